@@ -96,6 +96,52 @@ def build_batch(n_msgs: int, payload_bytes: int, n_topics: int, seed: int):
     return bytes(buf), offsets, wire_len
 
 
+# --dump-outputs budget: the ring sample is stored as float32 (4 B per ring
+# byte), so 8 Mi sampled ring bytes = 32 MiB on disk, well under 64 MB total
+DUMP_SAMPLE_USERS = 64
+DUMP_SAMPLE_RING_BYTES = 8 << 20
+
+
+def dump_outputs(out_dir, eng, wpos, rec, sort_by_seq, suffix=""):
+    """Write what the last timed step delivered, as float .npy arrays:
+
+      ring_wpos      [n_users]   every ring cursor the step's drain returned
+      sample_users   [S]         a fixed, seeded sample of user indices
+      ring_sample    [S, L]      the first L bytes of each sampled user's
+                                 egress ring (bytes past the user's cursor
+                                 zeroed: they are stale, not delivered)
+
+    rec is the uniform ring record stride. sort_by_seq orders each sampled
+    ring's records by their sequence header first: direct-delivery slots are
+    claimed atomically, so their ring order may differ between two runs."""
+    import random
+
+    import numpy as np
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    wpos_np = wpos.numpy()
+    length = min(int(wpos_np.max()), eng.ring_bytes)
+    length = max(rec, min(length, DUMP_SAMPLE_RING_BYTES) // rec * rec)
+    n_sample = max(1, min(eng.n_users, DUMP_SAMPLE_USERS, DUMP_SAMPLE_RING_BYTES // length))
+    # both ends of the population first, then the seeded picks
+    picks = [0, eng.n_users - 1] + random.Random(0).sample(range(eng.n_users), n_sample)
+    users = sorted(list(dict.fromkeys(picks))[:n_sample])
+    sample = np.zeros((len(users), length), dtype=np.float32)
+    for row, u in enumerate(users):
+        used = min(int(wpos_np[u]), length)
+        ring = np.frombuffer(eng.read_ring(u, used), dtype=np.uint8)
+        if sort_by_seq and used >= rec:
+            recs = ring[: used // rec * rec].reshape(-1, rec)
+            seq = recs[:, 4:8].copy().view("<u4").ravel()
+            ring = recs[np.argsort(seq, kind="stable")].ravel()
+            used = ring.size
+        sample[row, :used] = ring
+    np.save(out / f"ring_wpos{suffix}.npy", wpos_np.astype(np.float64))
+    np.save(out / f"sample_users{suffix}.npy", np.asarray(users, dtype=np.float64))
+    np.save(out / f"ring_sample{suffix}.npy", sample)
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -119,6 +165,12 @@ def main() -> None:
     p.add_argument("--graph", action="store_true",
                    help="hipGraph-capture the tick (measured ~2%% slower than "
                         "eager at this kernel count; kept for A/B)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step delivered "
+                        "(ring cursors + a seeded sample of egress rings) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure; a plain "
+                        "run already does nothing else, so today this adds none")
     args = p.parse_args()
     if args.mode == "mixed" and args.payload == 1024:
         args.payload = 65536  # config-4 default
@@ -230,7 +282,7 @@ def main() -> None:
             dev_bufs[0].copy_(pinned[0], non_blocking=True)
             copy_done[0].record(copy_stream)
 
-    def step(i: int) -> None:
+    def step(i: int) -> torch.Tensor:
         v = i % n_variants
         if use_cpu:
             buf = pinned[v]
@@ -270,7 +322,7 @@ def main() -> None:
             )
         if not use_cpu:
             tick_done[i % 2].record(torch.cuda.current_stream())
-        eng.drain_cursors()
+        return eng.drain_cursors()
 
     def barrier_sync() -> None:
         mesh.barrier()
@@ -282,10 +334,11 @@ def main() -> None:
     barrier_sync()
 
     step_times = []
+    last_wpos = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         s = time.perf_counter()
-        step(args.warmup + i)
+        last_wpos = step(args.warmup + i)
         if not use_cpu:
             torch.cuda.synchronize()
         step_times.append(time.perf_counter() - s)
@@ -295,6 +348,11 @@ def main() -> None:
 
     # MAX elapsed over ranks (the slowest rank defines the job)
     elapsed = mesh.max_over_ranks(elapsed)
+
+    if args.dump_outputs and last_wpos is not None:
+        dump_outputs(args.dump_outputs, eng, last_wpos, ring_rec(wire_len),
+                     sort_by_seq=(args.mode == "mixed"),
+                     suffix=f"_rank{rank}" if world_size > 1 else "")
 
     total_msgs = world_size * args.batch * args.steps
     msgs_per_sec = total_msgs / elapsed

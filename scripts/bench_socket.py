@@ -142,14 +142,19 @@ async def run_sender(args) -> None:
     pump = cid = None
     if hasattr(conn, "pump_handle"):   # tcp-native fast path (send_raw bursts)
         pump, cid = conn.pump_handle()
+    # connected and authenticated: only now does the coordinator fix the
+    # measurement window, so a slow process start cannot eat into it
+    print("READY", flush=True)
+    line = await asyncio.get_running_loop().run_in_executor(None, sys.stdin.readline)
+    t0, t1 = json.loads(line)
     now = time.time()
-    if args.t0 > now:
-        await asyncio.sleep(args.t0 - now)
+    if t0 > now:
+        await asyncio.sleep(t0 - now)
     sent = 0
     burst = max(1, int(args.rate / 500))  # ~500 pacing wakeups/s
     blob = bytearray(framed * burst)
     stride = len(framed)
-    while time.time() < args.t1:
+    while time.time() < t1:
         deadline = time.time() + burst / args.rate
         for j in range(burst):
             struct.pack_into("<d", blob, j * stride + 4 + payload_off, time.time())
@@ -251,22 +256,28 @@ async def run_coordinator(args) -> None:
         line = await p.stdout.readline()
         assert line.strip() == b"READY", line
 
-    t0 = time.time() + 1.0
-    t1 = t0 + args.seconds
-    window = json.dumps([t0, t1]).encode() + b"\n"
-    for p in sub_procs:
-        p.stdin.write(window)
-        await p.stdin.drain()
-
     send_procs = []
     for s in range(args.senders):
         p = await asyncio.create_subprocess_exec(
             sys.executable, __file__, "--role", "send", "--endpoint", ep,
             "--seed", str(5000 + s), "--rate", str(args.rate / args.senders),
-            "--payload", str(args.payload), "--t0", str(t0), "--t1", str(t1),
+            "--payload", str(args.payload),
             "--transport", args.transport,
-            stdout=asyncio.subprocess.PIPE)
+            stdin=asyncio.subprocess.PIPE, stdout=asyncio.subprocess.PIPE)
         send_procs.append(p)
+
+    # the window opens only once every sender is connected too: a slow
+    # process start must not eat into it
+    for p in send_procs:
+        line = await p.stdout.readline()
+        assert line.strip() == b"READY", line
+
+    t0 = time.time() + 1.0
+    t1 = t0 + args.seconds
+    window = json.dumps([t0, t1]).encode() + b"\n"
+    for p in sub_procs + send_procs:
+        p.stdin.write(window)
+        await p.stdin.drain()
 
     sent = 0
     for p in send_procs:
@@ -330,8 +341,6 @@ def main():
     p.add_argument("--ring-bytes", type=int, default=1 << 23)
     p.add_argument("--tick-s", type=float, default=0.002)
     p.add_argument("--device", default=None)
-    p.add_argument("--t0", type=float, default=0)
-    p.add_argument("--t1", type=float, default=0)
     p.add_argument("--tag", default="")
     p.add_argument("--pump-shards", type=int, default=4)
     p.add_argument("--count-mode", action="store_true")

@@ -40,6 +40,46 @@ def test_bench_json_contract():
     assert abs(cfg["deliveries_per_sec_node"] / d["value"] - 64) < 1e-6
 
 
+def test_bench_dump_outputs_deterministic(tmp_path):
+    """--dump-outputs writes the last timed step's deliveries as float .npy
+    arrays, identical from run to run (and with or without --full), and the
+    sampled rings hold exactly the batch's wire messages in arrival order."""
+    import numpy as np
+
+    sys.path.insert(0, str(REPO))
+    import bench
+    from pushcdn_amd.broker.gpu_engine import ring_rec
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    da = run_bench("--dump-outputs", str(a), "--full")
+    db = run_bench("--dump-outputs", str(b))
+    assert da["metric"] == db["metric"] and da["steps"] == db["steps"] == 2
+    names = sorted(f.name for f in a.iterdir())
+    assert names == ["ring_sample.npy", "ring_wpos.npy", "sample_users.npy"]
+    total = 0
+    for n in names:
+        xa, xb = np.load(a / n), np.load(b / n)
+        assert xa.dtype in (np.float32, np.float64)
+        assert xa.shape == xb.shape and np.array_equal(xa, xb), n
+        total += xa.nbytes
+    assert total <= 64 * 10**6
+
+    # last timed step is step index warmup+steps-1 = 2 -> batch variant 2
+    buf, offsets, wire_len = bench.build_batch(8, 1024, 8, seed=2)
+    rec = ring_rec(wire_len)
+    wpos = np.load(a / "ring_wpos.npy")
+    assert wpos.shape == (64,) and (wpos == 8 * rec).all()
+    users = np.load(a / "sample_users.npy")
+    assert users[0] == 0 and users[-1] == 63 and len(set(users)) == len(users)
+    rings = np.load(a / "ring_sample.npy")
+    assert rings.shape == (len(users), 8 * rec)
+    ring0 = rings[0].astype(np.uint8).tobytes()
+    for i in range(8):
+        got = ring0[i * rec + 16 : i * rec + 16 + wire_len]
+        assert got == buf[offsets[i] : offsets[i + 1]], i
+    assert (rings == rings[0]).all()  # every subscriber got the same stream
+
+
 def test_bench_mixed_contract():
     d = run_bench("--mode", "mixed", "--payload", "2048", "--topics", "4")
     assert d["metric"] == "broadcast_msgs_per_sec" or "msgs" in d["metric"]
