@@ -83,6 +83,18 @@ static inline hipStream_t cur_stream() {
     return at::hip::getCurrentHIPStream().stream();
 }
 
+// The flat K3 kernels index units with an exact u32 magic division
+// (csrc/common/divmagic.h) that holds only for d <= 2^21 and f < 2^31, and
+// truncate the flat unit index to u32: refuse shapes outside that envelope
+// instead of silently misplacing records.
+static inline void check_flat_shape(const torch::Tensor& pairs, int64_t units_per_pair) {
+    TORCH_CHECK(units_per_pair >= 1 && units_per_pair <= (int64_t(1) << 21),
+                "units_per_pair must be in [1, 2^21], got ", units_per_pair);
+    TORCH_CHECK(pairs.size(0) * units_per_pair < (int64_t(1) << 31),
+                "pair capacity * units_per_pair must be < 2^31, got ", pairs.size(0), " * ",
+                units_per_pair);
+}
+
 std::vector<torch::Tensor> parse_batch(torch::Tensor buf, torch::Tensor offsets,
                                        uint64_t hash_seed) {
     CHECK_DEV(buf); CHECK_CONTIG(buf); CHECK_DEV(offsets); CHECK_CONTIG(offsets);
@@ -308,6 +320,8 @@ void fanout_flat2(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor pa
                   int64_t seq_base, torch::Tensor n_pairs, int64_t units_per_pair,
                   torch::Tensor egress, int64_t nt, int64_t grid, int64_t uniform_len) {
     CHECK_DEV(egress); CHECK_CONTIG(egress);
+    pair_ptr(pairs);
+    check_flat_shape(pairs, units_per_pair);
     int32_t capacity = (int32_t)pairs.size(0);
     launch_k3_fanout_flat2(buf.data_ptr<uint8_t>(), payload_off.data_ptr<int64_t>(),
                            payload_len.data_ptr<int32_t>(), pair_ptr(pairs),
@@ -321,6 +335,8 @@ void fanout_flat3(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor pa
                   torch::Tensor seq_state, torch::Tensor n_pairs, int64_t units_per_pair,
                   torch::Tensor egress, int64_t nt, int64_t grid, int64_t uniform_len) {
     CHECK_DEV(egress); CHECK_CONTIG(egress);
+    pair_ptr(pairs);
+    check_flat_shape(pairs, units_per_pair);
     int32_t capacity = (int32_t)pairs.size(0);
     launch_k3_fanout_flat3(buf.data_ptr<uint8_t>(), payload_off.data_ptr<int64_t>(),
                            payload_len.data_ptr<int32_t>(), pair_ptr(pairs),

@@ -50,6 +50,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../common/divmagic.h"
+
 #define WAVE 64
 #ifndef CDN_CHECK
 #define CDN_CHECK 1
@@ -718,15 +720,9 @@ __global__ void __launch_bounds__(256) k3_fanout_flat_t(
     }
 }
 
-// exact u32 division-by-constant: p = (f * m) >> sh for all f < 2^31,
-// 1 <= d <= 2^21 (Granlund-Montgomery with one headroom bit: l = ceil_log2 d,
-// m = ceil(2^(31+l)/d) < 2^32, sh = 31+l; m*d - 2^(31+l) < d <= 2^l)
-static inline void u32_div_magic(int32_t d, uint32_t* m, int32_t* sh) {
-    int l = 0;
-    while ((1u << l) < (uint32_t)d) ++l;  // ceil_log2(d), d >= 1
-    *m = (uint32_t)(((1ull << (31 + l)) + (uint64_t)d - 1) / (uint64_t)d);
-    *sh = 31 + l;
-}
+// u32_div_magic (csrc/common/divmagic.h): p = (f * m) >> sh, exact for all
+// f < 2^31 and 1 <= d <= 2^21 — the bindings enforce both bounds
+// (units_per_pair <= 2^21, capacity * units_per_pair < 2^31) before launch.
 
 extern "C" void launch_k3_fanout_flat2(
     const uint8_t* buf, const int64_t* payload_off, const int32_t* payload_len,

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../bls/bls.h"
+#include "../common/divmagic.h"
 #include "../net/pump.h"
 #include "../net/udp_stream.h"
 #include "../state/versioned_map.h"
@@ -524,7 +525,48 @@ static int test_adversarial_parsers() {
     return 0;
 }
 
+// u32_div_magic backs the flat K3 fan-out's unit -> pair index: for every
+// divisor the kernel may see (units_per_pair <= 2^21) the multiplier must
+// fit u32 and (f*m)>>sh must equal f/d over the whole f < 2^31 domain —
+// checked at the domain ends and around every multiple-of-d boundary class
+static int test_u32_div_magic_exact() {
+    std::vector<int32_t> ds;
+    for (int32_t d = 1; d <= 4200; ++d) ds.push_back(d);
+    for (int k = 0; k <= 21; ++k) {
+        int32_t p = 1 << k;
+        if (p - 1 >= 1) ds.push_back(p - 1);
+        ds.push_back(p);
+        if (p + 1 <= (1 << 21)) ds.push_back(p + 1);
+    }
+    const uint64_t fmax = (1ull << 31) - 1;
+    for (int32_t d : ds) {
+        uint32_t m;
+        int32_t sh;
+        u32_div_magic(d, &m, &sh);
+        // the untruncated multiplier, recomputed in 64 bits
+        int l = 0;
+        while ((1ull << l) < (uint64_t)d) ++l;
+        const uint64_t m64 = ((1ull << (31 + l)) + (uint64_t)d - 1) / (uint64_t)d;
+        CHECK(m64 < (1ull << 32));
+        CHECK((uint64_t)m == m64);
+        CHECK(sh == 31 + l && sh < 64);
+        auto exact = [&](uint64_t f) { return (((uint64_t)(uint32_t)f * m) >> sh) == f / (uint64_t)d; };
+        for (uint64_t f : {0ull, 1ull, (unsigned long long)fmax, (unsigned long long)fmax - 1})
+            CHECK(exact(f));
+        const uint64_t qmax = fmax / (uint64_t)d;
+        for (uint64_t q : {1ull, 2ull, (unsigned long long)(qmax / 2),
+                           (unsigned long long)(qmax - 1), (unsigned long long)qmax}) {
+            for (uint64_t f : {q * d - 1, q * d, q * d + (uint64_t)d - 1}) {
+                if (f > fmax) continue;  // outside the kernel's f < 2^31 domain
+                CHECK(exact(f));
+            }
+        }
+    }
+    return 0;
+}
+
 int main() {
+    if (test_u32_div_magic_exact()) return 1;
     if (test_wire_roundtrip()) return 1;
     if (test_wire_fuzz_no_crash()) return 1;
     if (test_field_arithmetic()) return 1;

@@ -78,6 +78,14 @@ class GpuBrokerEngine:
         # records (wave idles tail lanes), wave won by ~3% at >=4 KiB
         # before the magic-division address math — env knob for A/B
         self._flat_max_rec = int(os.environ.get("PUSHCDN_FLAT_MAX_REC", "4096"))
+        # the flat kernel's unit index is a u32 with an exact magic division
+        # only for units_per_pair <= 2^21 and capacity * units < 2^31 (the
+        # bindings check the same per launch) — fail a bad config here
+        flat_units = self._flat_max_rec // 16 + 1
+        assert 1 <= flat_units <= (1 << 21), "PUSHCDN_FLAT_MAX_REC too large"
+        assert pair_capacity * flat_units < (1 << 31), (
+            f"pair_capacity {pair_capacity} x {flat_units} flat units/record "
+            "must stay below 2^31")
         self.nt_fanout = nt_fanout
         self.direct_enabled = direct_enabled
         # hash_seed keys the routing hash (keyhash.derive_routing_seed from

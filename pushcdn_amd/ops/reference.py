@@ -12,7 +12,7 @@ Semantics match the reference broker: topic match = union of subscriber sets
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -142,8 +142,14 @@ def fanout(
     pair_dst: torch.Tensor,
     msg_seq: torch.Tensor,
     egress: bytearray,
+    zero_pad_to: Optional[int] = None,
 ) -> None:
-    """Mirror of k3_fanout: write {u32 len, u32 seq, 8B pad} + payload."""
+    """Mirror of k3_fanout: write {u32 len, u32 seq, 8B pad} + payload.
+
+    By default exactly 16+len bytes are written per record (k3_fanout and
+    the wave kernel).  ``zero_pad_to=rec`` additionally zeroes
+    [dst+16+len, dst+rec): the flat kernels' full-stride contract (every
+    16 B unit of the record stride is stored, pad units as zeros)."""
     import struct
 
     for p in range(pair_user.shape[0]):
@@ -155,6 +161,46 @@ def fanout(
         dst = int(pair_dst[p])
         struct.pack_into("<IIII", egress, dst, length, int(msg_seq[m]) & 0xFFFFFFFF, 0, 0)
         egress[dst + 16 : dst + 16 + length] = buf[off : off + length]
+        if zero_pad_to is not None and zero_pad_to > 16 + length:
+            egress[dst + 16 + length : dst + zero_pad_to] = bytes(zero_pad_to - 16 - length)
+
+
+def apply_subs(
+    sub_bitmap: torch.Tensor,  # int64 [256][W] (bit-cast u64), mutated
+    buf: bytes,
+    topics_off: torch.Tensor,
+    topics_cnt: torch.Tensor,
+    disc: torch.Tensor,
+    user_idx: torch.Tensor,
+) -> None:
+    """Mirror of k2c_apply_subs: Subscribe (5) / Unsubscribe (6) updates
+    applied serially IN MESSAGE ORDER; other kinds and user_idx < 0 skipped."""
+    for m in range(disc.shape[0]):
+        d = int(disc[m])
+        if d != 5 and d != 6:
+            continue
+        u = int(user_idx[m])
+        if u < 0:
+            continue
+        w, bit = u >> 6, 1 << (u & 63)
+        off, cnt = int(topics_off[m]), int(topics_cnt[m])
+        for t in buf[off : off + cnt]:
+            # u64 arithmetic, then the two's-complement cast back (bit 63)
+            word = int(sub_bitmap[t, w]) & ((1 << 64) - 1)
+            word = (word | bit) if d == 5 else (word & ~bit & ((1 << 64) - 1))
+            sub_bitmap[t, w] = _i64(word)
+
+
+def compact_rings(egress: bytes, ring_bytes: int, wpos) -> Tuple[List[int], bytes]:
+    """Mirror of k7_compact_rings: every ring's used prefix, concatenated in
+    ring order.  Returns (offsets, staging bytes); offsets is the exclusive
+    scan of wpos with N+1 entries (ring u occupies [offsets[u], offsets[u+1]))."""
+    offsets = [0]
+    out = bytearray()
+    for u, n in enumerate(int(x) for x in wpos):
+        out += egress[u * ring_bytes : u * ring_bytes + n]
+        offsets.append(offsets[-1] + n)
+    return offsets, bytes(out)
 
 
 def direct_lookup(table_keys: torch.Tensor, table_vals: torch.Tensor, query: torch.Tensor) -> torch.Tensor:

@@ -30,7 +30,9 @@ def build(n_msgs):
 
 def bench_tick(batch, steps=30, grid=0):
     eng = GpuBrokerEngine(device="cuda:0", n_users=10000, ring_bytes=1 << 22,
-                          fanout_wire=True, direct_enabled=False, pair_capacity=8 << 20)
+                          fanout_wire=True, direct_enabled=False,
+                          # flat K3 index limit: capacity x 257 units < 2^31
+                          pair_capacity=8_000_000)
     eng.subscribe_all(list(range(8)))
     buf, offsets, wl = build(batch)
     dbuf, doff = eng.ingest(buf, offsets)

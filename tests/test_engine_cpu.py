@@ -148,3 +148,116 @@ def test_parse_ring_records_seq_sort_with_wrap():
     # no-wrap ordinary case
     ring2 = rec(7, b"y") + rec(5, b"x") + rec(9, b"z")
     assert [p for _, p in parse_ring_records(ring2, len(ring2))] == [b"x", b"y", b"z"]
+
+
+# ---- reference models used by the GPU golden tests, checked against
+# ---- independent host code so a wrong model cannot hide a wrong kernel
+
+def test_ref_compact_rings_matches_cpu_drain_compact():
+    """ref.compact_rings == the CPU branch of drain_compact(): used prefixes
+    in ring order, offsets = exclusive scan, empty rings between used ones."""
+    import random
+
+    import torch
+
+    from pushcdn_amd.ops import reference as ref
+
+    rng = random.Random(41)
+    eng = new_engine(n_users=9, ring_bytes=1 << 10)
+    eng.egress.copy_(torch.frombuffer(bytearray(rng.randbytes(9 << 10)), dtype=torch.uint8))
+    used = [0, 16, 1024, 0, 0, 48, 1008, 0, 512]   # empty, full, empty tail ring
+    eng.ring_wpos.copy_(torch.tensor(used, dtype=torch.int64))
+    egress = eng.egress.numpy().tobytes()
+    offsets_r, staging_r = ref.compact_rings(egress, eng.ring_bytes, used)
+    wpos, offsets, staging = eng.drain_compact()
+    assert wpos.tolist() == used
+    assert offsets.tolist() == offsets_r and len(offsets_r) == 10
+    assert staging.numpy().tobytes() == staging_r
+    assert len(staging_r) == sum(used)
+    assert int(eng.ring_wpos.sum()) == 0
+    # all-empty
+    assert ref.compact_rings(egress, eng.ring_bytes, [0] * 9) == ([0] * 10, b"")
+
+
+def test_ref_apply_subs_matches_engine_subscribe_unsubscribe():
+    """ref.apply_subs (the K2c model) == the same updates applied in order
+    through engine.subscribe / engine.unsubscribe, incl. bit 63, topic 255,
+    duplicate topics, skipped kinds and user_idx < 0."""
+    import random
+
+    import torch
+
+    from pushcdn_amd.ops import reference as ref
+
+    rng = random.Random(17)
+    n_users = 130
+    eng = new_engine(n_users=n_users)
+    eng.subscribe(63, [255, 0])           # pre-existing state incl. bit 63
+    eng.subscribe(129, [7])
+    sub = eng.sub_bitmap.clone()
+    users = [0, 63, 64, 127, 128, 129]
+    msgs, uidx = [], []
+    for i in range(150):
+        k = rng.randrange(10)
+        topics = [rng.choice([0, 1, 7, 255, rng.randrange(256)])
+                  for _ in range(rng.randrange(0, 5))]
+        if k < 4:
+            msgs.append(m.Subscribe(topics))
+        elif k < 8:
+            msgs.append(m.Unsubscribe(topics))
+        elif k == 8:
+            msgs.append(m.Broadcast(topics, b"not-a-sub"))
+        else:
+            msgs.append(m.UserSync(b"x"))
+        uidx.append(-1 if rng.random() < 0.1 else rng.choice(users))
+    batch, offsets = make_batch(msgs)
+    pr = ref.parse_batch(batch, offsets)
+    ref.apply_subs(sub, batch, pr.topics_off, pr.topics_cnt, pr.disc,
+                   torch.tensor(uidx, dtype=torch.int32))
+    for msg, u in zip(msgs, uidx):
+        if u < 0:
+            continue
+        if isinstance(msg, m.Subscribe):
+            eng.subscribe(u, list(msg.topics))
+        elif isinstance(msg, m.Unsubscribe):
+            eng.unsubscribe(u, list(msg.topics))
+    assert torch.equal(sub, eng.sub_bitmap)
+    assert int((sub != 0).sum()) > 0
+
+
+def test_ref_fanout_zero_pad_to():
+    """zero_pad_to zeroes exactly [dst+16+len, dst+rec); the default writes
+    exactly 16+len bytes and nothing else."""
+    import torch
+
+    from pushcdn_amd.ops import reference as ref
+
+    buf = bytes(range(1, 41))
+    poff = torch.tensor([3], dtype=torch.int64)
+    plen = torch.tensor([21], dtype=torch.int32)
+    args = (buf, poff, plen, torch.tensor([0], dtype=torch.int32),
+            torch.tensor([0], dtype=torch.int32), torch.tensor([16], dtype=torch.int64),
+            torch.tensor([-2], dtype=torch.int32))
+    a, b = bytearray(b"\xa5" * 96), bytearray(b"\xa5" * 96)
+    ref.fanout(*args, a)
+    ref.fanout(*args, b, zero_pad_to=64)
+    hdr = (21).to_bytes(4, "little") + (0xFFFFFFFE).to_bytes(4, "little") + bytes(8)
+    assert bytes(a) == b"\xa5" * 16 + hdr + buf[3:24] + b"\xa5" * (96 - 53)
+    assert bytes(b) == b"\xa5" * 16 + hdr + buf[3:24] + bytes(80 - 53) + b"\xa5" * 16
+
+
+def test_engine_rejects_pair_capacity_beyond_flat_index():
+    """pair_capacity x (largest flat record's 16 B units) must stay below
+    2^31, the exact range of the flat fan-out's u32 unit index: a config
+    outside it fails at construction, the largest one inside it is accepted
+    up to that check."""
+    import pytest
+
+    units = 4096 // 16 + 1
+    limit = ((1 << 31) - 1) // units          # largest capacity with cap*units < 2^31
+    assert limit * units < (1 << 31) <= (limit + 1) * units
+    with pytest.raises(AssertionError):
+        GpuBrokerEngine(device="cpu", n_users=2, ring_bytes=256, use_gpu_ops=False,
+                        pair_capacity=limit + 1)
+    GpuBrokerEngine(device="cpu", n_users=2, ring_bytes=256, use_gpu_ops=False,
+                    pair_capacity=limit)
