@@ -68,6 +68,15 @@ void launch_k2b_fused_t(const uint64_t*, const int32_t*, int32_t, int32_t, int32
 void launch_k2b_blocks_t(const uint64_t*, int32_t, int32_t, int32_t, int64_t, int32_t,
                          int32_t, uint64_t*, int32_t*, int32_t*, int32_t*, int32_t*,
                          int32_t*, int64_t*, PairRec*, uint32_t*, hipStream_t);
+void launch_k2a_topic_mask_origin_t(const uint64_t*, const uint8_t*, const int64_t*,
+                                    const int32_t*, const int32_t*, const int32_t*, uint64_t*,
+                                    int32_t, int32_t, int32_t, hipStream_t);
+void launch_k5b_emit_direct_peers(const int32_t*, const int32_t*, const int32_t*,
+                                  const int64_t*, const int32_t*, int32_t, int32_t, int32_t,
+                                  int64_t, int32_t, uint64_t*, int32_t*, PairRec*, uint32_t*,
+                                  hipStream_t);
+void launch_k6_direct_apply(uint64_t*, int32_t*, int64_t, const uint64_t*, const int32_t*,
+                            int32_t, const uint64_t*, int32_t, uint32_t*, hipStream_t);
 }
 
 #define CHECK_DEV(x) TORCH_CHECK(x.is_cuda(), #x " must be on the GPU")
@@ -423,7 +432,78 @@ void emit_direct(torch::Tensor disc, torch::Tensor owner, torch::Tensor payload_
                            (uint32_t*)drops.data_ptr<int32_t>(), cur_stream());
 }
 
+torch::Tensor topic_mask_origin_t(torch::Tensor sub_bitmap, torch::Tensor buf,
+                                  torch::Tensor topics_off, torch::Tensor topics_cnt,
+                                  torch::Tensor disc, torch::Tensor origin, int64_t n_users) {
+    CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap); CHECK_DEV(origin); CHECK_CONTIG(origin);
+    int32_t W = (int32_t)sub_bitmap.size(1);
+    int32_t M = (int32_t)disc.size(0);
+    TORCH_CHECK(origin.dtype() == torch::kInt32 && origin.numel() == M,
+                "origin must be an int32 [M] tensor");
+    TORCH_CHECK(n_users >= 0 && n_users <= (int64_t)W * 64, "n_users outside the bitmap");
+    auto mask_t = torch::empty({(int64_t)W, M},
+                               torch::TensorOptions().dtype(torch::kInt64).device(buf.device()));
+    if (M > 0) {
+        launch_k2a_topic_mask_origin_t(
+            (const uint64_t*)sub_bitmap.data_ptr<int64_t>(), buf.data_ptr<uint8_t>(),
+            topics_off.data_ptr<int64_t>(), topics_cnt.data_ptr<int32_t>(),
+            disc.data_ptr<int32_t>(), origin.data_ptr<int32_t>(),
+            (uint64_t*)mask_t.data_ptr<int64_t>(), M, W, (int32_t)n_users, cur_stream());
+    }
+    return mask_t;
+}
+
+void emit_direct_peers(torch::Tensor disc, torch::Tensor owner, torch::Tensor origin,
+                       torch::Tensor payload_off, torch::Tensor payload_len,
+                       int64_t ring_bytes, int64_t n_users, int64_t n_peers,
+                       torch::Tensor ring_wpos, torch::Tensor n_pairs, torch::Tensor pairs,
+                       torch::Tensor drops) {
+    int32_t M = (int32_t)disc.size(0);
+    if (M == 0) return;
+    CHECK_DEV(origin); CHECK_CONTIG(origin); CHECK_DEV(ring_wpos); CHECK_CONTIG(ring_wpos);
+    TORCH_CHECK(origin.dtype() == torch::kInt32 && origin.numel() == M,
+                "origin must be an int32 [M] tensor");
+    TORCH_CHECK(owner.numel() == M && payload_len.numel() == M);
+    TORCH_CHECK(n_users >= 0 && n_peers >= 0 && ring_wpos.numel() >= n_users + n_peers,
+                "ring_wpos must cover n_users + n_peers rings");
+    int32_t capacity = (int32_t)pairs.size(0);
+    launch_k5b_emit_direct_peers(
+        disc.data_ptr<int32_t>(), owner.data_ptr<int32_t>(), origin.data_ptr<int32_t>(),
+        payload_off.data_ptr<int64_t>(), payload_len.data_ptr<int32_t>(), M,
+        (int32_t)n_users, (int32_t)n_peers, ring_bytes, capacity,
+        (uint64_t*)ring_wpos.data_ptr<int64_t>(), n_pairs.data_ptr<int32_t>(),
+        pair_ptr(pairs), (uint32_t*)drops.data_ptr<int32_t>(), cur_stream());
+}
+
+void direct_apply(torch::Tensor table_keys, torch::Tensor table_vals, torch::Tensor up_keys,
+                  torch::Tensor up_owners, torch::Tensor del_keys, torch::Tensor n_failed) {
+    CHECK_DEV(table_keys); CHECK_DEV(table_vals); CHECK_DEV(up_keys); CHECK_DEV(up_owners);
+    CHECK_DEV(del_keys); CHECK_DEV(n_failed);
+    CHECK_CONTIG(table_keys); CHECK_CONTIG(table_vals); CHECK_CONTIG(up_keys);
+    CHECK_CONTIG(up_owners); CHECK_CONTIG(del_keys);
+    int64_t S = table_keys.size(0);
+    TORCH_CHECK(S > 0 && (S & (S - 1)) == 0, "table size must be a power of two");
+    TORCH_CHECK(table_vals.numel() == S && table_keys.dtype() == torch::kInt64
+                && table_vals.dtype() == torch::kInt32);
+    TORCH_CHECK(up_keys.dtype() == torch::kInt64 && del_keys.dtype() == torch::kInt64
+                && up_owners.dtype() == torch::kInt32 && n_failed.dtype() == torch::kInt32);
+    TORCH_CHECK(up_owners.numel() == up_keys.numel() && n_failed.numel() >= 1);
+    launch_k6_direct_apply((uint64_t*)table_keys.data_ptr<int64_t>(),
+                           table_vals.data_ptr<int32_t>(), S,
+                           (const uint64_t*)up_keys.data_ptr<int64_t>(),
+                           up_owners.data_ptr<int32_t>(), (int32_t)up_keys.numel(),
+                           (const uint64_t*)del_keys.data_ptr<int64_t>(),
+                           (int32_t)del_keys.numel(),
+                           (uint32_t*)n_failed.data_ptr<int32_t>(), cur_stream());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("topic_mask_origin_t", &topic_mask_origin_t,
+          "K2a transposed with per-message origin: remote-origin rows keep user bits only");
+    m.def("emit_direct_peers", &emit_direct_peers,
+          "K5b with peer recipient slots (owner -(p+2) -> ring n_users+p, local origin only)");
+    m.def("direct_apply", &direct_apply,
+          "K6: batched DirectMap upserts/deletes on the device table");
     m.def("parse_batch", &parse_batch, "K4: on-device capnp parse of a message batch",
           py::arg("buf"), py::arg("offsets"), py::arg("hash_seed") = 0);
     m.def("topic_mask", &topic_mask, "K2a: per-message subscriber mask");

@@ -36,6 +36,11 @@
 //   K5b k5b_emit_direct — on-device direct-delivery pair emission (appends
 //                        to the same pair list; no host sync)
 //   K2c k2c_apply_subs — ordered subscription updates
+//   K2a k2a_topic_mask_origin_t / K5b k5b_emit_direct_peers — the same two
+//                        steps with peer-broker recipient slots and a
+//                        per-message origin (single-hop broker plane)
+//   K6  k6_direct_apply — batched DirectMap upserts/deletes (CAS insert,
+//                        tombstoned values)
 //
 // Design notes (per /opt/skills/guides/cdna_hip_programming.md):
 //  - wave = 64; all copies are uint4 (16 B/lane) vectorized
@@ -1160,3 +1165,210 @@ extern "C" void launch_k7_compact_rings(const uint8_t* egress, int64_t ring_byte
     hipLaunchKernelGGL(k7_compact_rings, dim3(n_rings, max_chunks), dim3(256), 0, s,
                        egress, ring_bytes, wpos, dst_off, staging);
 }
+
+// ---------------------------------------------------------------------------
+// Peer-broker recipients.  The recipient index space is R = n_users + P:
+// recipient n_users + p is the egress ring of peer slot p, which takes each
+// message at most once per tick like a user subscribed to the peer's topics,
+// so K2b / K3 / K7 serve it unchanged.  The two kernels below add the
+// single-hop rule (reference to_users_only, broker/handler.rs:197-272): a
+// message that ARRIVED from a peer broker (origin != 0) never reaches a peer
+// ring.
+// ---------------------------------------------------------------------------
+
+// Bits of mask word w that belong to local users (recipients < n_users).
+__device__ inline uint64_t user_bits_of_word(int32_t w, int32_t n_users) {
+    const int64_t lo = (int64_t)w * 64;
+    if ((int64_t)n_users >= lo + 64) return ~0ull;
+    if ((int64_t)n_users <= lo) return 0ull;
+    return (1ull << (n_users - lo)) - 1ull;
+}
+
+// K2a with origin: k2a_topic_mask_t, except that a remote-origin message
+// keeps only its local-user bits.
+extern "C" __global__ void k2a_topic_mask_origin_t(
+    const uint64_t* __restrict__ sub_bitmap,  // [256][W], W = ceil(R/64)
+    const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ topics_off,
+    const int32_t* __restrict__ topics_cnt,
+    const int32_t* __restrict__ disc,
+    const int32_t* __restrict__ origin,       // [M] 0 = local user, else peer broker
+    uint64_t* __restrict__ mask_t,            // [W][M]
+    int32_t M, int32_t W, int32_t n_users)
+{
+    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)M * W) return;
+    int m = idx / W;
+    int w = idx % W;
+    uint64_t acc = 0;
+    if (disc[m] == 4) {
+        const uint8_t* topics = buf + topics_off[m];
+        int n = topics_cnt[m];
+        for (int t = 0; t < n; ++t) acc |= sub_bitmap[(int64_t)topics[t] * W + w];
+        if (origin[m] != 0) acc &= user_bits_of_word(w, n_users);
+    }
+    mask_t[(int64_t)w * M + m] = acc;
+}
+
+// K5b with peers: k5b_emit_direct, plus owner <= -2 -> peer slot
+// p = -owner-2.  A local-origin Direct to a key owned by peer p < P claims
+// space in ring n_users + p; a remote-origin one, a slot >= P and the
+// not-found value emit nothing and count no drop.  A non-negative owner
+// outside [0, n_users) is not a user ring and emits nothing either.
+extern "C" __global__ void k5b_emit_direct_peers(
+    const int32_t* __restrict__ disc,
+    const int32_t* __restrict__ owner,        // K5 output
+    const int32_t* __restrict__ origin,       // [M]
+    const int64_t* __restrict__ payload_off,
+    const int32_t* __restrict__ payload_len,
+    int32_t M, int32_t n_users, int32_t n_peers,
+    int64_t ring_bytes, int32_t capacity,
+    uint64_t* __restrict__ ring_wpos,         // [n_users + n_peers]
+    int32_t* __restrict__ n_pairs,
+    PairRec* __restrict__ pairs,
+    uint32_t* __restrict__ drops)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    if (disc[i] != 3) return;
+    const int32_t o = owner[i];
+    int u;
+    if (o >= 0) {
+        if (o >= n_users) return;
+        u = o;
+    } else {
+        // o <= -2 -> p >= 0; o == -1 -> p == -1; INT32_MIN -> p == 2^31 - 2
+        const int64_t p = -(int64_t)o - 2;
+        if (p < 0 || p >= (int64_t)n_peers || origin[i] != 0) return;
+        u = n_users + (int)p;
+    }
+    int32_t len = payload_len[i];
+    uint64_t rec = ring_rec(len);
+    int slot = atomicAdd(n_pairs, 1);
+    if (slot >= capacity) {
+        atomicAdd(drops, 1u);
+        return;
+    }
+    // CAS claim, exactly as k5b_emit_direct
+    unsigned long long cur = atomicAdd((unsigned long long*)&ring_wpos[u], 0ull);
+    while (true) {
+        if (cur + rec > (uint64_t)ring_bytes) {
+            store_pair(pairs + slot, -1, i, 0);  // K3 skips user<0 pairs
+            atomicAdd(drops, 1u);
+            return;
+        }
+        unsigned long long prev = atomicCAS((unsigned long long*)&ring_wpos[u], cur,
+                                            cur + (unsigned long long)rec);
+        if (prev == cur) break;
+        cur = prev;
+    }
+    store_pair(pairs + slot, u, i, (int64_t)u * ring_bytes + (int64_t)cur);
+}
+
+// ---------------------------------------------------------------------------
+// K6: batched incremental DirectMap updates.  One thread per update; the
+// first n_up threads upsert {key, owner}, the next n_del delete {key}.
+//   upsert: linear probe from key & mask with a 64-bit CAS(keys[slot], 0,
+//           key); an old value of 0 (claimed now) or key (already present)
+//           means the slot is this key's -> vals[slot] = owner.
+//   delete: probe to the key and store vals[slot] = INT32_MIN (K5's
+//           not-found value); the KEY STAYS.  Keys are never cleared, so
+//           "no empty slot between a key's home and the key" holds under
+//           concurrent inserts, and a re-upsert of a deleted key finds its
+//           old slot again.
+// Probing is bounded by table_size; an upsert that finds no slot bumps
+// n_failed[0] (read by the host on the control path only).  Key 0 is the
+// empty marker and is skipped.  Contract: the keys of one batch are
+// distinct (the host deduplicates, last write wins).
+// Between the key CAS and the value store a NEW slot holds its key with
+// whatever value the slot had (0 = local user 0 in a fresh table), so every
+// K5 reader must be ordered after this launch: K6 and the tick's K5 are
+// issued on the same stream, and nothing may look the table up from another
+// stream while a K6 launch is in flight.
+// When two NEW keys race for one probe chain, which of them gets the
+// earlier slot depends on CAS arrival order, so slot placement may differ
+// from run to run; lookup results do not.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void k6_direct_apply(
+    uint64_t* __restrict__ table_keys,
+    int32_t* __restrict__ table_vals,
+    int64_t table_size,                      // power of two
+    const uint64_t* __restrict__ up_keys,    // [n_up]
+    const int32_t* __restrict__ up_owners,   // [n_up]
+    int32_t n_up,
+    const uint64_t* __restrict__ del_keys,   // [n_del]
+    int32_t n_del,
+    uint32_t* __restrict__ n_failed)         // [1]
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_up + n_del) return;
+    const uint64_t mask = (uint64_t)table_size - 1;
+    if (i < n_up) {
+        const uint64_t key = up_keys[i];
+        if (key == 0) return;
+        const uint64_t s = key & mask;
+        for (int64_t probe = 0; probe < table_size; ++probe) {
+            const uint64_t slot = (s + probe) & mask;
+            const unsigned long long old = atomicCAS(
+                (unsigned long long*)&table_keys[slot], 0ull, (unsigned long long)key);
+            if (old == 0ull || old == (unsigned long long)key) {
+                table_vals[slot] = up_owners[i];
+                return;
+            }
+        }
+        atomicAdd(n_failed, 1u);
+        return;
+    }
+    const uint64_t key = del_keys[i - n_up];
+    if (key == 0) return;
+    const uint64_t s = key & mask;
+    for (int64_t probe = 0; probe < table_size; ++probe) {
+        const uint64_t slot = (s + probe) & mask;
+        const uint64_t k = __hip_atomic_load(&table_keys[slot], __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+        if (k == key) { table_vals[slot] = INT32_MIN; return; }
+        if (k == 0) return;   // absent: nothing to delete
+    }
+}
+
+extern "C" {
+
+void launch_k2a_topic_mask_origin_t(const uint64_t* sub_bitmap, const uint8_t* buf,
+                                    const int64_t* topics_off, const int32_t* topics_cnt,
+                                    const int32_t* disc, const int32_t* origin,
+                                    uint64_t* mask_t, int32_t M, int32_t W, int32_t n_users,
+                                    hipStream_t s) {
+    if (M <= 0) return;
+    int64_t total = (int64_t)M * W;
+    int threads = 256;
+    int64_t blocks = (total + threads - 1) / threads;
+    hipLaunchKernelGGL(k2a_topic_mask_origin_t, dim3((uint32_t)blocks), dim3(threads), 0, s,
+                       sub_bitmap, buf, topics_off, topics_cnt, disc, origin, mask_t, M, W,
+                       n_users);
+}
+
+void launch_k5b_emit_direct_peers(
+    const int32_t* disc, const int32_t* owner, const int32_t* origin,
+    const int64_t* payload_off, const int32_t* payload_len, int32_t M, int32_t n_users,
+    int32_t n_peers, int64_t ring_bytes, int32_t capacity, uint64_t* ring_wpos,
+    int32_t* n_pairs, PairRec* pairs, uint32_t* drops, hipStream_t s) {
+    if (M <= 0) return;
+    int threads = 256, blocks = (M + threads - 1) / threads;
+    hipLaunchKernelGGL(k5b_emit_direct_peers, dim3(blocks), dim3(threads), 0, s, disc, owner,
+                       origin, payload_off, payload_len, M, n_users, n_peers, ring_bytes,
+                       capacity, ring_wpos, n_pairs, pairs, drops);
+}
+
+void launch_k6_direct_apply(uint64_t* table_keys, int32_t* table_vals, int64_t table_size,
+                            const uint64_t* up_keys, const int32_t* up_owners, int32_t n_up,
+                            const uint64_t* del_keys, int32_t n_del, uint32_t* n_failed,
+                            hipStream_t s) {
+    const int total = n_up + n_del;
+    if (total <= 0) return;
+    int threads = 256, blocks = (total + threads - 1) / threads;
+    hipLaunchKernelGGL(k6_direct_apply, dim3(blocks), dim3(threads), 0, s, table_keys,
+                       table_vals, table_size, up_keys, up_owners, n_up, del_keys, n_del,
+                       n_failed);
+}
+
+}  // extern "C"

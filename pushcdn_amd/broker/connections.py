@@ -50,6 +50,10 @@ class SyncMap:
     def get(self, key: bytes) -> Optional[bytes]:
         return self._m.get(key)
 
+    def items(self) -> List[Tuple[bytes, bytes]]:
+        """Live (key, value) pairs."""
+        return list(self._m.items())
+
     def diff_bytes(self) -> bytes:
         if self._native:
             return self._m.diff()
@@ -166,13 +170,19 @@ class Connections:
     def apply_user_sync(self, data: bytes) -> List[UserPubKey]:
         """Merge a remote user delta; returns local users to kick (now owned
         elsewhere — reference connections/mod.rs:154-162)."""
+        return self.apply_user_sync_changes(data)[0]
+
+    def apply_user_sync_changes(self, data: bytes):
+        """apply_user_sync that also returns the merge's change list
+        [(pubkey, old owner, new owner)] — the GPU plane turns it into one
+        batched DirectMap update."""
         changed = self.direct_map.merge_bytes(data)
         me = str(self.identity).encode()
         to_kick = []
         for key, _old, new in changed:
             if new is not None and new != me and key in self.users:
                 to_kick.append(key)
-        return to_kick
+        return to_kick, changed
 
     def _local_topic_updates(self) -> None:
         """Refresh the TopicSyncMap from the current local user interest set

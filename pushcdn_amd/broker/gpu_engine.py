@@ -11,10 +11,13 @@ Owns the HBM-resident state and drives the kernel pipeline per tick:
       -> K5 direct_lookup                [DirectMap get]
 
 State tensors (all owned by PyTorch, sized for 288 GB HBM):
-  sub_bitmap  int64 [256][W]      subscription bitmap (W = ceil(n_users/64))
-  egress      uint8 [n_users*ring_bytes]  per-user egress rings
-  ring_wpos   int64 [n_users]     ring write cursors (device)
+  sub_bitmap  int64 [256][W]      subscription bitmap (W = ceil(R/64))
+  egress      uint8 [R*ring_bytes]  per-recipient egress rings
+  ring_wpos   int64 [R]           ring write cursors (device)
   direct_keys/vals                open-addressing DirectMap (u64 hash -> owner)
+
+R = n_users + n_peer_slots: recipients [0, n_users) are local users,
+recipient n_users + p is peer broker slot p (DirectMap owner -(p+2)).
 
 Delivery record format in a ring: {u32 len, u32 seq, u64 pad} + payload,
 16-byte aligned.  A drain (the socket-write analog) reads the cursors back,
@@ -34,6 +37,9 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from ..utils.keyhash import fnv1a64
+from ..utils.log import get_logger
+
+log = get_logger("gpu-engine")
 
 RING_ALIGN = 16
 
@@ -68,7 +74,17 @@ class GpuBrokerEngine:
         nt_fanout: bool = True,
         direct_enabled: bool = True,
         hash_seed: int = 0,
+        n_peer_slots: int = 0,
     ) -> None:
+        # n_peer_slots (P): peer brokers as recipients of the device
+        # pipeline.  The recipient index space is R = n_users + P; peer slot
+        # p is recipient n_users + p with its own egress ring, and owner
+        # value -(p+2) in the DirectMap.  A peer takes each message at most
+        # once per tick, like a user subscribed to the peer's topics, so
+        # K2b / K3 / K7 serve it unchanged.  n_users stays the LOCAL users.
+        assert n_peer_slots >= 0
+        self.n_peer_slots = n_peer_slots
+        self.n_recipients = n_users + n_peer_slots
         # pair_capacity bounds the preallocated delivery-pair buffers (the
         # sync-free pipeline drops + counts beyond it); nt_fanout uses
         # non-temporal egress stores; direct_enabled can be turned off for
@@ -112,16 +128,21 @@ class GpuBrokerEngine:
         assert ring_bytes % 16 == 0
         self.n_users = n_users
         self.ring_bytes = ring_bytes
-        self.W = (n_users + 63) // 64
+        R = self.n_recipients
+        self.W = (R + 63) // 64
 
         dev = self.device
         self.sub_bitmap = torch.zeros((256, self.W), dtype=torch.int64, device=dev)
-        self.egress = torch.zeros(n_users * ring_bytes, dtype=torch.uint8, device=dev)
-        self.ring_wpos = torch.zeros(n_users, dtype=torch.int64, device=dev)
+        self.egress = torch.zeros(R * ring_bytes, dtype=torch.uint8, device=dev)
+        self.ring_wpos = torch.zeros(R, dtype=torch.int64, device=dev)
         self.direct_keys = torch.zeros(direct_table_size, dtype=torch.int64, device=dev)
         self.direct_vals = torch.zeros(direct_table_size, dtype=torch.int32, device=dev)
         self._direct_entries: Dict[int, int] = {}
         self._direct_pubkeys: Dict[int, bytes] = {}  # hash -> full key (collision refusal)
+        # hashes whose key still sits in the device table with a tombstoned
+        # value (apply_direct_updates deletes); cleared by every rebuild
+        self._direct_tombstones: set = set()
+        self._direct_failed = torch.zeros(1, dtype=torch.int32, device=dev)
         self.seq = 0
         self.total = TickStats()
         self._staging_dev: Optional[torch.Tensor] = None
@@ -153,12 +174,56 @@ class GpuBrokerEngine:
 
     def subscribe_all(self, topics: List[int]) -> None:
         """Subscribe every user to the given topics (bulk, for benches)."""
+        if self.n_peer_slots:
+            # user bits only: peer-slot bits of the row are kept
+            full = self._user_bit_words().to(self.device)
+            for t in topics:
+                self.sub_bitmap[t & 0xFF] |= full
+            return
         full = torch.full((self.W,), -1, dtype=torch.int64)
         tail = self.n_users & 63
         if tail:
             full[-1] = (1 << tail) - 1
         for t in topics:
             self.sub_bitmap[t & 0xFF] = full.to(self.device)
+
+    def _user_bit_words(self) -> torch.Tensor:
+        """int64 [W]: the bits of every bitmap word that belong to local
+        users (recipients below n_users)."""
+        words = torch.zeros(self.W, dtype=torch.int64)
+        nfull = self.n_users >> 6
+        words[:nfull] = -1
+        tail = self.n_users & 63
+        if tail:
+            words[nfull] = (1 << tail) - 1
+        return words
+
+    # ------------------------------ peer slots ------------------------------
+
+    def _peer_word_bit(self, p: int) -> Tuple[int, int]:
+        if not 0 <= p < self.n_peer_slots:
+            raise IndexError(f"peer slot {p} outside [0, {self.n_peer_slots})")
+        r = self.n_users + p
+        bit = 1 << (r & 63)
+        return r >> 6, (bit - (1 << 64) if bit >= (1 << 63) else bit)
+
+    def set_peer_topics(self, p: int, topics: List[int]) -> None:
+        """Make `topics` the exact interest set of peer slot p: a local
+        Broadcast on any of them lands once in ring n_users + p."""
+        w, bit = self._peer_word_bit(p)
+        self.sub_bitmap[:, w] &= ~bit
+        rows = sorted({t & 0xFF for t in topics})
+        if rows:
+            self.sub_bitmap[torch.tensor(rows, device=self.device), w] |= bit
+
+    def clear_peer(self, p: int) -> None:
+        """Release peer slot p: no topic reaches its ring any more and
+        whatever the ring still holds is discarded.  Its DirectMap entries
+        are the caller's to delete (direct_keys_owned_by +
+        apply_direct_updates)."""
+        w, bit = self._peer_word_bit(p)
+        self.sub_bitmap[:, w] &= ~bit
+        self.ring_wpos[self.n_users + p] = 0
 
     def _direct_hash(self, pubkey: bytes) -> int:
         """Routing hash of a pubkey, with collision refusal: if a DIFFERENT
@@ -173,7 +238,7 @@ class GpuBrokerEngine:
         return h
 
     def register_direct(self, pubkey: bytes, owner: int) -> None:
-        """owner >= 0: local user index. owner < 0: -(broker_rank+2)."""
+        """owner >= 0: local user index. owner <= -2: peer slot -(p+2)."""
         h = self._direct_hash(pubkey)
         self._direct_pubkeys[h] = pubkey
         self._direct_entries[h] = owner
@@ -208,7 +273,11 @@ class GpuBrokerEngine:
             bits = np.zeros(self.W, dtype=np.uint64)
             np.bitwise_or.at(bits, words, np.uint64(1) << (sel & 63).astype(np.uint64))
             bitmap[t] = bits
-        self.sub_bitmap.copy_(torch.from_numpy(bitmap.view(np.int64)).to(self.device))
+        new = torch.from_numpy(bitmap.view(np.int64)).to(self.device)
+        if self.n_peer_slots:
+            # user bits only: carry the peer-slot bits over
+            new |= self.sub_bitmap & ~self._user_bit_words().to(self.device)
+        self.sub_bitmap.copy_(new)
 
     def _rebuild_direct_table(self) -> None:
         from ..ops.reference import build_direct_table
@@ -218,19 +287,130 @@ class GpuBrokerEngine:
         )
         self.direct_keys.copy_(keys.to(self.device))
         self.direct_vals.copy_(vals.to(self.device))
+        self._direct_tombstones.clear()
+
+    def direct_keys_owned_by(self, owner: int) -> List[bytes]:
+        """Pubkeys whose DirectMap entry currently holds `owner`."""
+        return [self._direct_pubkeys[h] for h, o in self._direct_entries.items()
+                if o == owner]
+
+    def apply_direct_updates(self, upserts, deletes) -> None:
+        """Batched incremental DirectMap update: `upserts` is a list of
+        (pubkey, owner), `deletes` a list of pubkeys.  One K6 launch (or the
+        CPU mirror) instead of a host rebuild + two table copies.
+
+        The host dicts stay the source of truth.  Within one call the last
+        upsert of a key wins, and an upsert wins over a delete of the same
+        key.  An entry whose hash collides with a DIFFERENT registered key
+        is skipped and logged (remote entries must not raise).  Deletes
+        tombstone the value and leave the key in its slot; when live +
+        tombstoned slots would pass half the table and there is a tombstone
+        to reclaim, or the kernel reports an update that found no slot, the
+        table is compacted by a rebuild.
+        Raises RuntimeError("direct table full") if the live entries alone
+        do not fit."""
+        ups: Dict[int, Tuple[bytes, int]] = {}
+        for pubkey, owner in upserts:
+            h = fnv1a64(pubkey, self.hash_seed)
+            prev = self._direct_pubkeys.get(h)
+            if prev is None and h in ups:
+                prev = ups[h][0]
+            if (prev is not None and prev != pubkey) or h == 0:
+                log.warning("direct routing-hash collision; skipping remote entry")
+                continue
+            ups[h] = (pubkey, int(owner))
+        dels: Dict[int, None] = {}   # insertion-ordered set
+        for pubkey in deletes:
+            h = fnv1a64(pubkey, self.hash_seed)
+            if h in ups or h in dels:
+                continue
+            if h in self._direct_entries and self._direct_pubkeys.get(h) == pubkey:
+                dels[h] = None
+        dels = list(dels)
+        S = self.direct_keys.shape[0]
+        live = len(self._direct_entries) - len(dels) + sum(
+            1 for h in ups if h not in self._direct_entries)
+        if live > S:
+            raise RuntimeError("direct table full")
+        new_slots = sum(1 for h in ups if h not in self._direct_entries
+                        and h not in self._direct_tombstones)
+        used = len(self._direct_entries) + len(self._direct_tombstones) + new_slots
+        for h in dels:
+            del self._direct_entries[h]
+            del self._direct_pubkeys[h]
+        for h, (pubkey, owner) in ups.items():
+            self._direct_entries[h] = owner
+            self._direct_pubkeys[h] = pubkey
+        if not ups and not dels:
+            return
+        tombstones = (self._direct_tombstones | set(dels)) - set(ups)
+        # compaction reclaims tombstoned slots only: with none, a table past
+        # half full keeps taking incremental inserts (probe chains grow, as
+        # in any open-addressing table; size gpu_direct_table_size at twice
+        # the cluster's users to stay below it) and falls back to the
+        # rebuild through n_failed
+        if used > S // 2 and tombstones:
+            self._rebuild_direct_table()
+            return
+        self._direct_tombstones = tombstones
+        up_list = [(h, o) for h, (_k, o) in ups.items()]
+        try:
+            if not self.use_gpu_ops:
+                from ..ops.reference import direct_apply
+
+                failed = direct_apply(self.direct_keys, self.direct_vals, up_list, dels)
+            else:
+                def i64(x: int) -> int:
+                    return x - (1 << 64) if x >= (1 << 63) else x
+
+                dev = self.device
+                up_keys = torch.tensor([i64(h) for h, _ in up_list],
+                                       dtype=torch.int64).to(dev)
+                up_owners = torch.tensor([o for _, o in up_list],
+                                         dtype=torch.int32).to(dev)
+                del_keys = torch.tensor([i64(h) for h in dels], dtype=torch.int64).to(dev)
+                self._ops.direct_apply(self.direct_keys, self.direct_vals, up_keys,
+                                       up_owners, del_keys, self._direct_failed)
+                failed = int(self._direct_failed.cpu()[0])  # control path only
+                if failed:
+                    self._direct_failed.zero_()
+        except Exception:
+            # the host dicts already hold the update: bring the device table
+            # back in line with them before the error travels on
+            self._rebuild_direct_table()
+            raise
+        if failed:
+            self._rebuild_direct_table()
 
     # ---------------------------- the hot tick ----------------------------
 
+    def _origin_tensor(self, origin, M: int) -> torch.Tensor:
+        """Per-message origin as an int32 [M] tensor on the engine device
+        (0 = from a local user, 1 = from a peer broker; None = all zeros)."""
+        if origin is None:
+            return torch.zeros(M, dtype=torch.int32, device=self.device)
+        if not isinstance(origin, torch.Tensor):
+            origin = torch.tensor(list(origin), dtype=torch.int32)
+        assert origin.numel() == M, "origin must have one entry per message"
+        return origin.to(device=self.device, dtype=torch.int32,
+                         non_blocking=self.is_cuda).contiguous()
+
     def ingest(self, batch: bytes, offsets: List[int],
-               staging: Optional[torch.Tensor] = None
-               ) -> Tuple[torch.Tensor, torch.Tensor]:
+               staging: Optional[torch.Tensor] = None, origin=None):
         """H2D-copy one batch of serialized messages. Returns device (buf, offsets).
+
+        `origin` (int32 [M] tensor or list; 0 = local user, 1 = peer broker)
+        is copied alongside: the return value is then (buf, offsets, origin)
+        with the device origin tensor to hand to tick().
 
         `staging`: an HBM-pool slice (hbm_pool.PoolBytes.tensor) to land the
         batch in instead of a fresh allocation — the bounded/backpressured
         ingest path (reference limiter semantics).  Safe to reuse after the
         caller drops the allocation because all consumers are stream-ordered
         behind this copy on the engine's stream."""
+        if origin is not None:
+            buf, off = self.ingest(batch, offsets, staging)
+            return buf, off, self._origin_tensor(origin, len(offsets) - 1)
         host = torch.frombuffer(bytearray(batch), dtype=torch.uint8)
         off = torch.tensor(offsets, dtype=torch.int64)
         if staging is not None:
@@ -247,22 +427,27 @@ class GpuBrokerEngine:
     def tick(self, buf: torch.Tensor, offsets: torch.Tensor,
              host_batch: Optional[bytes] = None,
              host_offsets: Optional[List[int]] = None,
-             uniform_wire_len: Optional[int] = None) -> TickStats:
+             uniform_wire_len: Optional[int] = None,
+             origin=None) -> TickStats:
         """Run the full pipeline on one ingested batch already on device.
 
         uniform_wire_len: if the caller knows every message in the batch has
         this exact wire length (and fanout_wire is set), the flat-index K3
-        variant runs at ~100% lane utilization."""
+        variant runs at ~100% lane utilization.
+
+        origin: per-message int32 [M] tensor or list, 0 = from a local user,
+        1 = from a peer broker (None = all local).  Remote-origin messages
+        never reach a peer ring (single hop)."""
         if self.use_gpu_ops:
-            return self._tick_gpu(buf, offsets, uniform_wire_len)
+            return self._tick_gpu(buf, offsets, uniform_wire_len, origin)
         assert host_batch is not None and host_offsets is not None
-        return self._tick_cpu(host_batch, host_offsets)
+        return self._tick_cpu(host_batch, host_offsets, origin)
 
     def _k2b_block_scratch(self, M: int):
         """Lazily (re)allocate the block-K2b scratch for batches up to M
         messages: [NB][W*64] counts + prefixes, per-user base/fit/dst."""
         NB = (M + 31) // 32
-        W64 = ((self.n_users + 63) // 64) * 64
+        W64 = self.W * 64
         cur = getattr(self, "_k2b_scratch", None)
         if cur is not None and cur[0] >= NB:
             return cur[1]
@@ -284,24 +469,33 @@ class GpuBrokerEngine:
         if rec and self.use_gpu_ops:
             bcount, pprefix, ubase, ufit, udst = self._k2b_block_scratch(M)
             ops.assign_emit_blocks_t(
-                mask_t, self.ring_wpos, self.ring_bytes, self.n_users,
+                mask_t, self.ring_wpos, self.ring_bytes, self.n_recipients,
                 bcount, pprefix, ubase, ufit, udst,
                 self._pairs, self._drops, self._n_pairs, rec,
             )
         else:
             ops.assign_emit_fused_t(
-                mask_t, payload_len, self.ring_wpos, self.ring_bytes, self.n_users,
+                mask_t, payload_len, self.ring_wpos, self.ring_bytes, self.n_recipients,
                 self._pairs, self._drops, self._n_pairs, rec,
             )
 
     def _tick_gpu(self, buf: torch.Tensor, offsets: torch.Tensor,
-                  uniform_wire_len: Optional[int] = None) -> TickStats:
+                  uniform_wire_len: Optional[int] = None, origin=None) -> TickStats:
         ops = self._ops
         M = offsets.shape[0] - 1
         disc, payload_off, payload_len, topics_off, topics_cnt, recip_hash, _ts = ops.parse_batch(
             buf, offsets, self.hash_seed
         )
-        mask_t = ops.topic_mask_t(self.sub_bitmap, buf, topics_off, topics_cnt, disc)
+        # peer plane: with peer slots or an explicit origin the origin-aware
+        # K2a / K5b variants run; otherwise exactly the kernels of a lone
+        # broker (topic_mask_t, emit_direct)
+        peer_plane = self.n_peer_slots > 0 or origin is not None
+        if peer_plane:
+            origin = self._origin_tensor(origin, M)
+            mask_t = ops.topic_mask_origin_t(self.sub_bitmap, buf, topics_off, topics_cnt,
+                                             disc, origin, self.n_users)
+        else:
+            mask_t = ops.topic_mask_t(self.sub_bitmap, buf, topics_off, topics_cnt, disc)
         if self.fanout_wire:
             payload_off = offsets[:-1].contiguous()
             payload_len = (offsets[1:] - offsets[:-1]).to(torch.int32).contiguous()
@@ -319,8 +513,14 @@ class GpuBrokerEngine:
             # (uniform_wire_len callers promise Direct messages share the
             # same padded wire length as broadcasts.)
             owner = ops.direct_lookup(self.direct_keys, self.direct_vals, recip_hash)
-            ops.emit_direct(disc, owner, payload_off, payload_len, self.ring_bytes,
-                            self.ring_wpos, self._n_pairs, self._pairs, self._drops)
+            if peer_plane:
+                ops.emit_direct_peers(disc, owner, origin, payload_off, payload_len,
+                                      self.ring_bytes, self.n_users, self.n_peer_slots,
+                                      self.ring_wpos, self._n_pairs, self._pairs,
+                                      self._drops)
+            else:
+                ops.emit_direct(disc, owner, payload_off, payload_len, self.ring_bytes,
+                                self.ring_wpos, self._n_pairs, self._pairs, self._drops)
         seq_base = self.seq
         self.seq += M
         nt = 1 if self.nt_fanout else 0
@@ -391,12 +591,14 @@ class GpuBrokerEngine:
             self._graphs[key] = g
         g.replay()
 
-    def _tick_cpu(self, batch: bytes, offsets: List[int]) -> TickStats:
+    def _tick_cpu(self, batch: bytes, offsets: List[int], origin=None) -> TickStats:
         from ..ops import reference as ref
 
         pr = ref.parse_batch(batch, offsets, self.hash_seed)
         M = len(offsets) - 1
-        mask = ref.topic_mask(self.sub_bitmap, batch, pr.topics_off, pr.topics_cnt, pr.disc)
+        origin = self._origin_tensor(origin, M)
+        mask = ref.topic_mask_origin(self.sub_bitmap, batch, pr.topics_off, pr.topics_cnt,
+                                     pr.disc, origin, self.n_users)
         if self.fanout_wire:
             pr.payload_off = torch.tensor(offsets[:-1], dtype=torch.int64)
             pr.payload_len = (
@@ -404,30 +606,22 @@ class GpuBrokerEngine:
                 - torch.tensor(offsets[:-1], dtype=torch.int64)
             ).to(torch.int32)
         pair_user, pair_msg, pair_dst, drops = ref.assign_emit(
-            mask, pr.payload_len, self.ring_wpos, self.ring_bytes, self.n_users
+            mask, pr.payload_len, self.ring_wpos, self.ring_bytes, self.n_recipients
         )
         seq = torch.arange(self.seq, self.seq + M, dtype=torch.int32)
         self.seq += M
         arr = bytearray(self.egress.numpy().tobytes())  # copy-in; copied back below
         ref.fanout(batch, pr.payload_off, pr.payload_len, pair_user, pair_msg, pair_dst, seq, arr)
+        # Direct deliveries claim ring space after the broadcasts, in message
+        # order: local users and, for local-origin messages, peer slots
         owner = ref.direct_lookup(self.direct_keys, self.direct_vals, pr.recip_hash)
-        for i in range(M):
-            if int(pr.disc[i]) == 3 and int(owner[i]) >= 0:
-                u = int(owner[i])
-                length = int(pr.payload_len[i])
-                rec = ring_rec(length)
-                wpos = int(self.ring_wpos[u])
-                if wpos + rec <= self.ring_bytes:
-                    dst = u * self.ring_bytes + wpos
-                    import struct
-
-                    struct.pack_into("<IIII", arr, dst, length, int(seq[i]) & 0xFFFFFFFF, 0, 0)
-                    arr[dst + 16 : dst + 16 + length] = batch[
-                        int(pr.payload_off[i]) : int(pr.payload_off[i]) + length
-                    ]
-                    self.ring_wpos[u] = wpos + rec
+        d_user, d_msg, d_dst, d_drops = ref.emit_direct_peers(
+            pr.disc, owner, origin, pr.payload_len, self.ring_wpos, self.ring_bytes,
+            self.n_users, self.n_peer_slots)
+        ref.fanout(batch, pr.payload_off, pr.payload_len, d_user, d_msg, d_dst, seq, arr)
         self.egress.copy_(torch.frombuffer(arr, dtype=torch.uint8))
-        return TickStats(n_messages=M, n_deliveries=int(pair_user.shape[0]), n_drops=drops)
+        return TickStats(n_messages=M, n_deliveries=int(pair_user.shape[0]),
+                         n_drops=drops + d_drops)
 
     # ------------------------------- drain ---------------------------------
 
@@ -448,11 +642,11 @@ class GpuBrokerEngine:
         (user/sender.rs:16-33)."""
         if not self.use_gpu_ops:
             wpos = self.drain_cursors()
-            offsets = torch.zeros(self.n_users + 1, dtype=torch.int64)
+            offsets = torch.zeros(self.n_recipients + 1, dtype=torch.int64)
             torch.cumsum(wpos, 0, out=offsets[1:])
             total = int(offsets[-1])
             staging = torch.empty(total, dtype=torch.uint8)
-            for u in range(self.n_users):
+            for u in range(self.n_recipients):
                 n = int(wpos[u])
                 if n:
                     s = u * self.ring_bytes
@@ -460,7 +654,7 @@ class GpuBrokerEngine:
             return wpos, offsets, staging
         wpos_dev = self.ring_wpos  # read by K7 before the reset below
         wpos = wpos_dev.detach().to("cpu")  # sync: cursor readback
-        offsets = torch.zeros(self.n_users + 1, dtype=torch.int64)
+        offsets = torch.zeros(self.n_recipients + 1, dtype=torch.int64)
         torch.cumsum(wpos, 0, out=offsets[1:])
         total = int(offsets[-1])
         if total == 0:
@@ -479,7 +673,7 @@ class GpuBrokerEngine:
                 torch.empty(cap, dtype=torch.uint8, pin_memory=self.is_cuda)
                 for _ in range(2)
             ]
-        dst_off = offsets[: self.n_users].to(self.device, non_blocking=True)
+        dst_off = offsets[: self.n_recipients].to(self.device, non_blocking=True)
         max_chunks = (int(wpos.max()) + (64 << 10) - 1) // (64 << 10)
         self._ops.compact_rings(self.egress, self.ring_bytes, wpos_dev, dst_off,
                                 self._staging_dev, max_chunks)

@@ -67,6 +67,8 @@ class MeshBroker(Broker):
     # C++ blob ingest is supported: the tick normalizes blob items into
     # per-message views for the collective pack
     BLOB_INGEST = True
+    # the broker plane is the collective: no device peer rings here
+    PEER_FORWARD = False
 
     def __init__(self, config: BrokerConfig, batch_capacity: int = 1 << 22,
                  interest_routed: Optional[bool] = None) -> None:

@@ -97,6 +97,13 @@ class BrokerConfig:
     # HBM message-pool budget for ingest staging (reference
     # --global-memory-pool-size default 1 GiB, broker.rs:71-73); 0 = off
     gpu_pool_bytes: int = 1 << 30
+    # broker-plane forwarding on the device: peer brokers become recipient
+    # slots of the kernel pipeline (own egress ring, bitmap bit, DirectMap
+    # owner), so the tick does no per-message host work with peers either.
+    # Off: the per-message Python forwarding of the tick task, as before.
+    gpu_peer_forward: bool = False
+    gpu_max_peers: int = 32
+    gpu_direct_table_size: int = 1 << 16
 
 
 @dataclass
@@ -113,6 +120,10 @@ class BrokerHandle:
 
 
 class Broker:
+    # MeshBroker overrides to False: its broker plane is the collective,
+    # so config.gpu_peer_forward has no effect there
+    PEER_FORWARD = True
+
     def __init__(self, config: BrokerConfig) -> None:
         from ..proto.transports.tcp import Tcp
 
@@ -136,15 +147,25 @@ class Broker:
         self._free_gpu_slots: List[int] = []
         self._drain_by_buffer: Dict[int, asyncio.Task] = {}
         self._last_drain: Optional[asyncio.Task] = None
+        # device peer forwarding: broker -> peer slot of the engine
+        self._peer_forward = (config.data_plane == "gpu" and config.gpu_peer_forward
+                              and type(self).PEER_FORWARD)
+        self._peer_slot_of: Dict[BrokerIdentifier, int] = {}
+        self._free_peer_slots: List[int] = []
+        self._peer_slots_exhausted_logged = False
         if config.data_plane == "gpu":
             from .gpu_engine import GpuBrokerEngine
 
             from ..utils.keyhash import derive_routing_seed
 
+            n_peer_slots = config.gpu_max_peers if self._peer_forward else 0
+            self._free_peer_slots = list(range(n_peer_slots - 1, -1, -1))
             self._engine = GpuBrokerEngine(
                 device=config.gpu_device,
                 n_users=config.gpu_max_users,
                 ring_bytes=config.gpu_ring_bytes,
+                direct_table_size=config.gpu_direct_table_size,
+                n_peer_slots=n_peer_slots,
                 fanout_wire=True,  # forward raw wire bytes verbatim
                 # keyed routing hash: cluster-wide secret derived from the
                 # shared broker private key (see keyhash.derive_routing_seed)
@@ -266,6 +287,7 @@ class Broker:
             if handle.task:
                 handle.task.cancel()
             handle.connection.close()
+        self._release_peer_slot(broker)
 
     # ------------------------------ user path ------------------------------
 
@@ -599,6 +621,7 @@ class Broker:
             if old.task:
                 old.task.cancel()
             old.connection.close()
+        self._claim_peer_slot(peer_identity)
         # initial full syncs (broker/handler.rs:98-117)
         await self.try_send_to_broker(
             peer_identity, Bytes(m.serialize(m.TopicSync(self.connections.get_full_topic_sync())))
@@ -637,25 +660,35 @@ class Broker:
                         continue
                     # single-hop mesh: deliver only to local users.  On the
                     # GPU plane that means routing through the ENGINE with
-                    # no re-forwarding (fwd=None) — the kernels only ever
-                    # write local rings, which IS to_users_only.
+                    # no re-forwarding (fwd=None): without peer slots the
+                    # kernels only ever write local rings, and with
+                    # gpu_peer_forward fwd=None becomes origin 1, which
+                    # keeps the message out of every peer ring — either
+                    # way to_users_only.
                     if self._engine is not None:
                         await self._gpu_queue.put((raw, None))
                     else:
                         await self.handle_broadcast_message(topics, raw, to_users_only=True)
                 elif isinstance(msg, m.Direct):
                     if self._engine is not None:
-                        # K5 drops non-local recipients = to_user_only
+                        # K5b emits for local owners only; a peer-slot
+                        # owner is skipped for origin 1 = to_user_only
                         await self._gpu_queue.put((raw, None))
                     else:
                         await self.handle_direct_message(msg.recipient, raw, to_user_only=True)
                 elif isinstance(msg, m.UserSync):
-                    to_kick = self.connections.apply_user_sync(msg.data)
+                    to_kick, changed = self.connections.apply_user_sync_changes(msg.data)
                     for pubkey in to_kick:
                         await self.remove_user(pubkey)
+                    if self._peer_forward:
+                        self._apply_user_sync_to_engine(changed)
                     raw.drop()
                 elif isinstance(msg, m.TopicSync):
                     self.connections.apply_topic_sync(peer, msg.data)
+                    slot = self._peer_slot_of.get(peer)
+                    if slot is not None:
+                        self._engine.set_peer_topics(slot, list(
+                            self.connections.broker_topics.get_values_by_key(str(peer))))
                     raw.drop()
                 else:
                     break
@@ -743,6 +776,74 @@ class Broker:
         self._engine.unsubscribe(slot, list(range(256)))
         self._free_gpu_slots.append(slot)
 
+    # --- peer slots (gpu_peer_forward): a connected broker as a recipient
+    # of the device pipeline ---
+
+    def _claim_peer_slot(self, broker: BrokerIdentifier) -> None:
+        """Give a just-connected peer a recipient slot of the engine: its
+        topic interests become bitmap bits and the users it owns DirectMap
+        entries -(slot+2).  With no slot free the peer stays on the Python
+        forwarding of the tick task."""
+        if not self._peer_forward:
+            return
+        slot = self._peer_slot_of.get(broker)
+        if slot is None:
+            if not self._free_peer_slots:
+                if not self._peer_slots_exhausted_logged:
+                    self._peer_slots_exhausted_logged = True
+                    log.warning("no free gpu peer slot (gpu_max_peers=%d): %s and later "
+                                "peers use host forwarding", self.config.gpu_max_peers, broker)
+                return
+            slot = self._free_peer_slots.pop()
+            self._peer_slot_of[broker] = slot
+        self._engine.set_peer_topics(
+            slot, list(self.connections.broker_topics.get_values_by_key(str(broker))))
+        owned = str(broker).encode()
+        self._apply_peer_direct(
+            [(key, -(slot + 2)) for key, val in self.connections.direct_map.items()
+             if val == owned and key not in self.connections.users], [])
+
+    def _release_peer_slot(self, broker: BrokerIdentifier) -> None:
+        slot = self._peer_slot_of.pop(broker, None)
+        if slot is None:
+            return
+        self._engine.clear_peer(slot)
+        # delete every device entry that points at the slot, so a later
+        # occupant never inherits them
+        self._apply_peer_direct([], self._engine.direct_keys_owned_by(-(slot + 2)))
+        self._free_peer_slots.append(slot)
+
+    def _apply_peer_direct(self, upserts, deletes) -> None:
+        if not upserts and not deletes:
+            return
+        try:
+            self._engine.apply_direct_updates(upserts, deletes)
+        except RuntimeError as exc:
+            # table full: remote users that did not fit are simply not
+            # routable from this broker (a Direct to them is dropped)
+            log.warning("gpu direct table: %s", exc)
+
+    def _apply_user_sync_to_engine(self, changed) -> None:
+        """One batched device update for a merged UserSync: new owner a peer
+        with a slot -> upsert; no owner or a broker without a slot -> delete;
+        this broker -> left to the local registration path."""
+        me = str(self.identity).encode()
+        upserts, deletes = [], []
+        for key, _old, new in changed:
+            if new == me or key in self.connections.users:
+                continue
+            slot = None
+            if new is not None:
+                try:
+                    slot = self._peer_slot_of.get(BrokerIdentifier.parse(new.decode()))
+                except Exception:
+                    slot = None
+            if slot is not None:
+                upserts.append((key, -(slot + 2)))
+            else:
+                deletes.append(key)
+        self._apply_peer_direct(upserts, deletes)
+
     async def _drain_egress(self) -> None:
         """One tick's egress: K7-compact every used ring into one staging
         buffer (one D2H), then hand the WHOLE tick to the C++ pump in one
@@ -764,6 +865,11 @@ class Broker:
                 # tick loop; the buffer is no longer being written either way
                 pass
         wpos, offsets, staging = self._engine.drain_compact()
+        # who owns each peer ring is fixed NOW, with the cursors: the
+        # dispatch runs later, and a slot released and re-claimed in between
+        # must not hand this tick's bytes to its new occupant
+        peers = [(broker, pslot, self.connections.brokers.get(broker))
+                 for broker, pslot in self._peer_slot_of.items()]
         prev = self._last_drain
 
         async def _dispatch_chained():
@@ -772,13 +878,15 @@ class Broker:
                     await asyncio.shield(prev)
                 except Exception:
                     pass
-            await self._dispatch_egress(wpos, offsets, staging)
+            await self._dispatch_egress(wpos, offsets, staging, peers)
 
         task = asyncio.get_running_loop().create_task(_dispatch_chained())
         self._drain_by_buffer[idx] = task
         self._last_drain = task
 
-    async def _dispatch_egress(self, wpos, offsets, staging) -> None:
+    async def _dispatch_egress(self, wpos, offsets, staging, peers=()) -> None:
+        """`peers`: [(broker, peer slot, handle)] as of the drain that
+        produced wpos/offsets/staging."""
         from .gpu_engine import parse_ring_records
 
         by_pump = {}        # pump -> [(pubkey, cid, start, end)]
@@ -800,6 +908,29 @@ class Broker:
                     (pubkey, cid, int(offsets[slot]), int(offsets[slot + 1])))
                 continue
             fallback.append((slot, pubkey, n))
+        # peer rings drain like user rings (records are whole wire messages);
+        # the recipient key is the BrokerIdentifier and a failed send removes
+        # the broker
+        peer_fallback = []  # (ring, broker, nbytes, handle)
+        n_users = self._engine.n_users
+        for broker, pslot, handle in peers:
+            ring_idx = n_users + pslot
+            n = int(wpos[ring_idx])
+            if n == 0:
+                continue
+            if handle is None or self.connections.brokers.get(broker) is not handle:
+                continue  # the peer left (or reconnected) since the drain
+            ph = getattr(handle.connection, "pump_handle", None)
+            if ph is not None:
+                try:
+                    p, cid = ph()
+                except Exception:
+                    await self.remove_broker(broker)
+                    continue
+                by_pump.setdefault(p, []).append(
+                    (broker, cid, int(offsets[ring_idx]), int(offsets[ring_idx + 1])))
+                continue
+            peer_fallback.append((ring_idx, broker, n, handle))
         if by_pump:
             # off-loop AND parallel: the coalescing memcpy releases the GIL
             # in C++ (frame building is lock-free), so sharding the users
@@ -829,9 +960,26 @@ class Broker:
                     cnt = flat[2 * i]
                     total_payload += flat[2 * i + 1]
                     if cnt < 0:
-                        await self.remove_user(pubkey)
+                        if isinstance(pubkey, BrokerIdentifier):
+                            await self.remove_broker(pubkey)
+                        else:
+                            await self.remove_user(pubkey)
             if total_payload:
                 BYTES_SENT.inc(total_payload)
+        for ring_idx, broker, n, handle in peer_fallback:
+            ring = bytes(staging[int(offsets[ring_idx]):int(offsets[ring_idx + 1])].numpy()
+                         .tobytes())
+            if self.connections.brokers.get(broker) is not handle:
+                continue
+            sink = getattr(handle.connection, "send_ring_records", None)
+            if sink is not None:
+                try:
+                    sink(ring, n)
+                except Exception:
+                    await self.remove_broker(broker)
+            else:
+                for _seq, payload in parse_ring_records(ring, n):
+                    await self.try_send_to_broker(broker, Bytes(payload))
         for slot, pubkey, n in fallback:
             ring = bytes(staging[int(offsets[slot]):int(offsets[slot + 1])].numpy()
                          .tobytes())
@@ -859,10 +1007,12 @@ class Broker:
             _users, brokers = self.connections.get_interested_by_topic(
                 list(data), to_users_only=False)
             for broker in brokers:
-                await self.try_send_to_broker(broker, raw.clone())
+                if broker not in self._peer_slot_of:  # slotted peers: device ring
+                    await self.try_send_to_broker(broker, raw.clone())
         else:
             owner = self.connections.get_broker_identifier_of_user(data)
-            if owner is not None and owner != self.identity:
+            if (owner is not None and owner != self.identity
+                    and owner not in self._peer_slot_of):
                 await self.try_send_to_broker(owner, raw.clone())
 
     async def _gpu_tick_task(self) -> None:
@@ -891,10 +1041,20 @@ class Broker:
             buf = bytearray()
             offsets = [0]
             have_peers = bool(self.connections.brokers)
+            # peers that hold a device slot are served by the kernels; only
+            # slot-less peers (gpu_max_peers exhausted) take the host loops
+            slotted = self._peer_slot_of
+            if slotted:
+                have_peers = any(b not in slotted for b in self.connections.brokers)
+            # per-message origin for the engine: 0 = from a local user,
+            # 1 = from a peer broker (fwd is None), never re-forwarded
+            origin = [] if self._peer_forward else None
             legacy = []  # Bytes to drop after the tick
             for item in batch:
                 if item[0] == "blob":
                     _tag, blob, ends, fwds = item
+                    if origin is not None:
+                        origin.extend([0] * len(ends))
                     if have_peers:
                         fs = 0
                         for i, fwd in enumerate(fwds):
@@ -905,12 +1065,15 @@ class Broker:
                                     _u, brokers = self.connections.get_interested_by_topic(
                                         list(blob[fs + s:fs + e]), to_users_only=False)
                                     for b in brokers:
+                                        if b in slotted:
+                                            continue
                                         await self.try_send_to_broker(
                                             b, Bytes(blob[fs:fe]))
                                 else:
                                     owner = self.connections.get_broker_identifier_of_user(
                                         blob[fs + s:fs + e])
-                                    if owner is not None and owner != self.identity:
+                                    if (owner is not None and owner != self.identity
+                                            and owner not in slotted):
                                         await self.try_send_to_broker(
                                             owner, Bytes(blob[fs:fe]))
                             fs = fe
@@ -920,6 +1083,8 @@ class Broker:
                 else:
                     raw, fwd = item
                     legacy.append(raw)
+                    if origin is not None:
+                        origin.append(1 if fwd is None else 0)
                     if have_peers and fwd is not None:
                         await self._forward_to_mesh(raw, fwd)
                     buf += raw.data
@@ -930,10 +1095,15 @@ class Broker:
             # matching the reference limiter (protocols/mod.rs:328)
             pb = await self._hbm_pool.alloc(len(buf)) if self._hbm_pool else None
             host = bytes(buf)
-            dbuf, doff = self._engine.ingest(
-                host, offsets, staging=pb.tensor if pb else None)
+            if origin is None:
+                dbuf, doff = self._engine.ingest(
+                    host, offsets, staging=pb.tensor if pb else None)
+            else:
+                dbuf, doff, origin = self._engine.ingest(
+                    host, offsets, staging=pb.tensor if pb else None, origin=origin)
             t2 = _time.perf_counter()
-            self._engine.tick(dbuf, doff, host_batch=host, host_offsets=offsets)
+            self._engine.tick(dbuf, doff, host_batch=host, host_offsets=offsets,
+                              origin=origin)
             t3 = _time.perf_counter()
             await self._drain_egress()
             t4 = _time.perf_counter()

@@ -89,6 +89,94 @@ def topic_mask(
     return mask
 
 
+def user_bits_of_word(w: int, n_users: int) -> int:
+    """Bits of mask word w that belong to local users (recipients below
+    n_users), as an unsigned 64-bit value — the kernels' closed form."""
+    lo = w * 64
+    if n_users >= lo + 64:
+        return (1 << 64) - 1
+    if n_users <= lo:
+        return 0
+    return (1 << (n_users - lo)) - 1
+
+
+def topic_mask_origin(
+    sub_bitmap: torch.Tensor,  # int64 [256][W], W = ceil((n_users + P) / 64)
+    buf: bytes,
+    topics_off: torch.Tensor,
+    topics_cnt: torch.Tensor,
+    disc: torch.Tensor,
+    origin,                    # [M] 0 = from a local user, else from a peer broker
+    n_users: int,
+) -> torch.Tensor:
+    """Mirror of k2a_topic_mask_origin_t (untransposed, [M][W]): topic_mask,
+    then every recipient bit >= n_users (the peer slots) is cleared for a
+    remote-origin message — single hop, the reference's to_users_only."""
+    mask = topic_mask(sub_bitmap, buf, topics_off, topics_cnt, disc)
+    W = sub_bitmap.shape[1]
+    for m in range(disc.shape[0]):
+        if int(origin[m]) == 0:
+            continue
+        for w in range(W):
+            word = int(mask[m, w]) & ((1 << 64) - 1)
+            mask[m, w] = _i64(word & user_bits_of_word(w, n_users))
+    return mask
+
+
+def emit_direct_peers(
+    disc: torch.Tensor,
+    owner: torch.Tensor,        # direct_lookup output
+    origin,                     # [M]
+    payload_len: torch.Tensor,
+    ring_wpos: torch.Tensor,    # int64 [n_users + n_peers], mutated
+    ring_bytes: int,
+    n_users: int,
+    n_peers: int,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:
+    """Mirror of k5b_emit_direct_peers, serial in message order (the kernel
+    claims atomically, so its pair ORDER is unspecified; the set of pairs
+    and the cursor totals are the same whenever no ring fills).  owner in
+    [0, n_users) is a local user; owner <= -2 is peer slot p = -owner-2,
+    reached only by a local-origin message and only if p < n_peers.
+    Returns (pair_user, pair_msg, pair_dst, drops); a full ring gives a
+    (-1, msg, 0) placeholder and one drop."""
+    pair_user: List[int] = []
+    pair_msg: List[int] = []
+    pair_dst: List[int] = []
+    drops = 0
+    for i in range(disc.shape[0]):
+        if int(disc[i]) != 3:
+            continue
+        o = int(owner[i])
+        if o >= 0:
+            if o >= n_users:
+                continue
+            u = o
+        else:
+            p = -o - 2
+            if p < 0 or p >= n_peers or int(origin[i]) != 0:
+                continue
+            u = n_users + p
+        rec = ring_rec(int(payload_len[i]))
+        wpos = int(ring_wpos[u])
+        if wpos + rec > ring_bytes:
+            pair_user.append(-1)
+            pair_msg.append(i)
+            pair_dst.append(0)
+            drops += 1
+            continue
+        pair_user.append(u)
+        pair_msg.append(i)
+        pair_dst.append(u * ring_bytes + wpos)
+        ring_wpos[u] = wpos + rec
+    return (
+        torch.tensor(pair_user, dtype=torch.int32),
+        torch.tensor(pair_msg, dtype=torch.int32),
+        torch.tensor(pair_dst, dtype=torch.int64),
+        drops,
+    )
+
+
 def assign_emit(
     mask: torch.Tensor,         # int64 [M][W]
     payload_len: torch.Tensor,  # int32 [M]
@@ -221,6 +309,55 @@ def direct_lookup(table_keys: torch.Tensor, table_vals: torch.Tensor, query: tor
             if k == 0:
                 break
     return out
+
+
+DIRECT_TOMBSTONE = -(2**31)  # INT32_MIN: direct_lookup's not-found value
+
+
+def direct_apply(
+    table_keys: torch.Tensor,   # int64 [S] (bit-cast u64), mutated
+    table_vals: torch.Tensor,   # int32 [S], mutated
+    upserts: List[Tuple[int, int]],   # (u64 key, owner)
+    deletes: List[int],               # u64 keys
+) -> int:
+    """Mirror of k6_direct_apply, serial: upserts in order, then deletes.
+    An upsert takes the first slot of its probe chain that is empty or
+    already holds the key; a delete stores the tombstone value and LEAVES
+    the key, so chains never break and a re-upsert reuses the slot.  Key 0
+    is skipped.  Returns the number of upserts that found no slot."""
+    S = table_keys.shape[0]
+    assert S & (S - 1) == 0
+    maskv = S - 1
+    u64 = (1 << 64) - 1
+    failed = 0
+    for h, owner in upserts:
+        h &= u64
+        if h == 0:
+            continue
+        s = h & maskv
+        for probe in range(S):
+            slot = (s + probe) & maskv
+            k = int(table_keys[slot]) & u64
+            if k == 0 or k == h:
+                table_keys[slot] = _i64(h)
+                table_vals[slot] = owner
+                break
+        else:
+            failed += 1
+    for h in deletes:
+        h &= u64
+        if h == 0:
+            continue
+        s = h & maskv
+        for probe in range(S):
+            slot = (s + probe) & maskv
+            k = int(table_keys[slot]) & u64
+            if k == h:
+                table_vals[slot] = DIRECT_TOMBSTONE
+                break
+            if k == 0:
+                break
+    return failed
 
 
 def build_direct_table(entries: List[Tuple[int, int]], size: int) -> Tuple[torch.Tensor, torch.Tensor]:
