@@ -432,6 +432,41 @@ PYBIND11_MODULE(pushcdn_core, m) {
                  return p.send_rings_batch((const uint8_t*)info.ptr, ids, starts, ends);
              },
              "batched tick drain: one call for all users' compacted rings")
+        .def("send_ring_ref", [](net::Pump& p, int64_t id, py::buffer ring, size_t wpos,
+                                 py::buffer ref) {
+            py::buffer_info info = ring.request();
+            py::buffer_info rinfo = ref.request();
+            if (wpos > (size_t)info.size) throw std::runtime_error("wpos beyond ring");
+            if (rinfo.itemsize != 1)
+                throw std::runtime_error("send_ring_ref: reference buffer must be bytes");
+            std::pair<int64_t, int64_t> r;
+            {
+                py::gil_scoped_release nogil;
+                r = p.send_ring(id, (const uint8_t*)info.ptr, wpos,
+                                (const uint8_t*)rinfo.ptr, (size_t)rinfo.size);
+            }
+            return py::make_tuple(r.first, r.second);
+        })
+        .def("send_rings_batch_ref",
+             [](net::Pump& p, py::buffer base, py::buffer ref, const std::vector<int64_t>& ids,
+                const std::vector<int64_t>& starts, const std::vector<int64_t>& ends) {
+                 py::buffer_info info = base.request();
+                 py::buffer_info rinfo = ref.request();
+                 if (rinfo.itemsize != 1)
+                     throw std::runtime_error(
+                         "send_rings_batch_ref: reference buffer must be bytes");
+                 if (ids.size() != starts.size() || ids.size() != ends.size())
+                     throw std::runtime_error("send_rings_batch_ref: length mismatch");
+                 for (size_t j = 0; j < ids.size(); ++j)
+                     if (starts[j] < 0 || ends[j] < starts[j] || ends[j] > info.size)
+                         throw std::runtime_error("send_rings_batch_ref: range beyond buffer");
+                 // by-reference records are range-checked against `ref` one
+                 // by one while the rings are parsed (build_ring_frames)
+                 py::gil_scoped_release nogil;
+                 return p.send_rings_batch((const uint8_t*)info.ptr, ids, starts, ends,
+                                           (const uint8_t*)rinfo.ptr, (size_t)rinfo.size);
+             },
+             "batched tick drain with a reference buffer for by-reference records")
         .def("set_ingest", &net::Pump::set_ingest)
         .def("recv_ingest", [](net::Pump& p, int64_t id) {
             auto b = p.recv_ingest(id);

@@ -47,6 +47,9 @@ void launch_k1_bls_verify_wave(const uint8_t*, const uint8_t*, uint8_t*, const i
 void launch_k1_dbg_wave(const uint8_t*, const uint8_t*, uint8_t*, const int64_t*,
                         const uint8_t*, const uint64_t*, int32_t, int32_t, int32_t*,
                         hipStream_t);
+void launch_k3_fanout_ref(const uint8_t*, const int64_t*, const int32_t*, const PairRec*,
+                          const uint32_t*, const int32_t*, int32_t, int32_t, int64_t,
+                          uint8_t*, int, int, hipStream_t);
 void launch_k3_fanout_wave(const uint8_t*, const int64_t*, const int32_t*, const PairRec*,
                            const uint32_t*, const int32_t*, int32_t, uint8_t*, int, int,
                            hipStream_t);
@@ -324,6 +327,23 @@ void fanout_wave(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor pay
                           (int)grid, cur_stream());
 }
 
+void fanout_ref(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor payload_len,
+                torch::Tensor pairs,
+                torch::Tensor msg_seq, torch::Tensor n_pairs, torch::Tensor egress,
+                int64_t nt, int64_t grid, int64_t ref_threshold, int64_t ref_base) {
+    CHECK_DEV(egress); CHECK_CONTIG(egress);
+    TORCH_CHECK(ref_threshold >= 0 && ref_threshold <= INT32_MAX,
+                "ref_threshold must fit an int32 length");
+    TORCH_CHECK(ref_base >= 0, "ref_base must not be negative");
+    launch_k3_fanout_ref(buf.data_ptr<uint8_t>(), payload_off.data_ptr<int64_t>(),
+                         payload_len.data_ptr<int32_t>(), pair_ptr(pairs),
+                         (const uint32_t*)msg_seq.data_ptr<int32_t>(),
+                         n_pairs.data_ptr<int32_t>(), (int32_t)pairs.size(0),
+                         (int32_t)ref_threshold, ref_base,
+                         egress.data_ptr<uint8_t>(), (int)nt,
+                         (int)grid, cur_stream());
+}
+
 void fanout_flat2(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor payload_len,
                   torch::Tensor pairs,
                   int64_t seq_base, torch::Tensor n_pairs, int64_t units_per_pair,
@@ -536,6 +556,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "exact per-item fallback)");
     m.def("hash_to_g1_batch", &hash_to_g1_batch, "K1 helper: batched hash-to-G1");
     m.def("fanout_wave", &fanout_wave, "K3v2: wave-per-pair fan-out (nt flag, device count)");
+    m.def("fanout_ref", &fanout_ref,
+          "K3r: fan-out with by-reference records at or above ref_threshold");
     m.def("fanout_flat2", &fanout_flat2, "K3v4: flat fan-out, seq from base, capacity clamp");
     m.def("fanout_flat3", &fanout_flat3, "K3v5: graph-capturable (device seq counter)");
     m.def("seq_advance", &seq_advance, "bump the device seq counter (inside the graph)");

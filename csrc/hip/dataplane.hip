@@ -31,6 +31,10 @@
 //                        reference variant for golden tests. All mirror the
 //                        reference's raw-bytes Arc-clone push
 //                        (user/sender.rs:16-33).
+//   K3r k3_fanout_ref_t — the mixed-size fan-out with by-reference records:
+//                        a message at or above ref_threshold is delivered
+//                        as a bare 16 B header that points into the host's
+//                        copy of the batch (up to 64 pairs per wave)
 //   K5  k5_direct_lookup — open-addressing probe user-hash -> owner
 //                        (reference connections/mod.rs:69-71 DirectMap get)
 //   K5b k5b_emit_direct — on-device direct-delivery pair emission (appends
@@ -647,6 +651,137 @@ void launch_k3_fanout_wave(const uint8_t* buf, const int64_t* payload_off,
                            egress);
 }
 
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// K3r: fan-out with by-reference delivery.  Same pair list as the wave
+// kernel; a message of at least ref_threshold bytes is delivered as a bare
+// 16 B header {u32 len | REF_FLAG, u32 seq, u64 ref_base + payload_off[msg]}
+// and its payload stays in the host's copy of the batch; any shorter message
+// is written exactly as k3_fanout_wave_t writes it.
+//
+// Work split: a wave owns G CONSECUTIVE pairs per grid-stride step, one
+// pair per lane (lanes >= G hold none).  The by-reference lanes store their
+// header together (one dword4 store per lane, one wave instruction for up to
+// G pairs) — a wave per pair would spend a whole wave on each 16 B store.
+// The wave then walks the ballot of inline lanes, broadcasts that lane's
+// pair through __shfl and copies the record cooperatively (64 lanes x 16 B
+// per pass), with the wave kernel's aligned / unaligned source branches,
+// byte tail and NT option.
+//
+// G is the smallest power of two, at most 64, at which one step of all the
+// grid's waves covers the pair list.  A fixed G = 64 was measured first: it
+// leaves a small tick on n_pairs / 64 waves, each copying its inline records
+// one after the other (8,000 inline pairs of 64 KiB: 1.24 ms against the
+// wave kernel's 0.16 ms; profiles/byref_delivery_fixed64.json).  With the adaptive G a list
+// shorter than the grid runs one pair per wave, exactly the wave kernel's
+// schedule, and only a list that oversubscribes the grid is packed, which is
+// also where the header stores are many enough to be worth packing.
+// ---------------------------------------------------------------------------
+#define REF_FLAG 0x80000000u
+
+template <int NT>
+__global__ void __launch_bounds__(256) k3_fanout_ref_t(
+    const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ payload_off,
+    const int32_t* __restrict__ payload_len,
+    const PairRec* __restrict__ pairs,
+    const uint32_t* __restrict__ msg_seq,
+    const int32_t* __restrict__ n_pairs_ptr,
+    int32_t capacity,
+    int32_t ref_threshold,
+    int64_t ref_base,
+    uint8_t* __restrict__ egress)
+{
+    int n_pairs = *n_pairs_ptr;
+    if (n_pairs > capacity) n_pairs = capacity;  // see k3_fanout_wave_t
+    const int lane = threadIdx.x & 63;
+    const int wave_in_wg = threadIdx.x >> 6;
+    const int waves_total = gridDim.x * 4;
+    int gs = 0;  // log2(G); n_pairs is wave-uniform, so this loop is scalar
+    while (gs < 6 && ((n_pairs - 1) >> gs) + 1 > waves_total) ++gs;
+    const int n_groups = n_pairs > 0 ? ((n_pairs - 1) >> gs) + 1 : 0;
+    for (int g = blockIdx.x * 4 + wave_in_wg; g < n_groups; g += waves_total) {
+        const int64_t p = ((int64_t)g << gs) + lane;
+        int32_t len = 0;
+        uint32_t seq = 0;
+        int64_t off = 0, dsto = 0;
+        bool live = false;
+        if (lane < (1 << gs) && p < n_pairs) {
+            const PairRec pr = pairs[p];
+            if (pr.user >= 0) {
+                live = true;
+                len = payload_len[pr.msg];
+                off = payload_off[pr.msg];
+                seq = msg_seq[pr.msg];
+                dsto = pr.dst;
+            }
+        }
+        const bool by_ref = live && len >= ref_threshold;
+        if (by_ref) {
+            const uint64_t ro = (uint64_t)(ref_base + off);
+            cdn_v4u h = {(uint32_t)len | REF_FLAG, seq, (uint32_t)ro, (uint32_t)(ro >> 32)};
+            if (NT) __builtin_nontemporal_store(h, (cdn_v4u*)(egress + dsto));
+            else *(cdn_v4u*)(egress + dsto) = h;
+        }
+        // every lane of the wave reaches the ballot and the shuffles below
+        unsigned long long inl = __ballot(live && !by_ref);
+        while (inl) {
+            const int j = __ffsll((long long)inl) - 1;
+            inl &= inl - 1;
+            const int32_t jlen = __shfl(len, j);
+            const uint32_t jseq = (uint32_t)__shfl((int)seq, j);
+            const int64_t joff = ((int64_t)__shfl((int)(off >> 32), j) << 32)
+                                 | (uint32_t)__shfl((int)off, j);
+            const int64_t jdst = ((int64_t)__shfl((int)(dsto >> 32), j) << 32)
+                                 | (uint32_t)__shfl((int)dsto, j);
+            const uint8_t* src = buf + joff;
+            uint8_t* dst = egress + jdst;
+            if (lane == 0) {
+                cdn_v4u h = {(uint32_t)jlen, jseq, 0u, 0u};
+                if (NT) __builtin_nontemporal_store(h, (cdn_v4u*)dst);
+                else *(cdn_v4u*)dst = h;
+            }
+            dst += 16;
+            const int32_t nvec = jlen >> 4;
+            if ((((uintptr_t)src) & 15) == 0) {
+                const cdn_v4u* s4 = (const cdn_v4u*)src;
+                cdn_v4u* d4 = (cdn_v4u*)dst;
+                for (int k = lane; k < nvec; k += 64) {
+                    cdn_v4u v = s4[k];
+                    if (NT) __builtin_nontemporal_store(v, d4 + k);
+                    else d4[k] = v;
+                }
+            } else {
+                for (int k = lane; k < nvec; k += 64) {
+                    uint8_t tmp[16];
+                    memcpy(tmp, src + (size_t)k * 16, 16);
+                    memcpy(dst + (size_t)k * 16, tmp, 16);
+                }
+            }
+            for (int k = (nvec << 4) + lane; k < jlen; k += 64) dst[k] = src[k];
+        }
+    }
+}
+
+extern "C" {
+
+void launch_k3_fanout_ref(const uint8_t* buf, const int64_t* payload_off,
+                          const int32_t* payload_len, const PairRec* pairs,
+                          const uint32_t* msg_seq, const int32_t* n_pairs_ptr,
+                          int32_t capacity, int32_t ref_threshold, int64_t ref_base,
+                          uint8_t* egress, int nt, int grid, hipStream_t s) {
+    if (grid <= 0) grid = 4096;  // 4096 WGs x 4 waves, up to 64 pairs per wave and step
+    if (nt)
+        hipLaunchKernelGGL((k3_fanout_ref_t<1>), dim3(grid), dim3(256), 0, s, buf, payload_off,
+                           payload_len, pairs, msg_seq, n_pairs_ptr, capacity,
+                           ref_threshold, ref_base, egress);
+    else
+        hipLaunchKernelGGL((k3_fanout_ref_t<0>), dim3(grid), dim3(256), 0, s, buf, payload_off,
+                           payload_len, pairs, msg_seq, n_pairs_ptr, capacity,
+                           ref_threshold, ref_base, egress);
+}
 
 }  // extern "C"
 

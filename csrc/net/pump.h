@@ -225,9 +225,12 @@ public:
     // (pushcdn_amd/broker/gpu_engine.py ring_rec / parse_ring_records).
     // The payload IS a serialized wire message, so it goes out verbatim.
     // Returns (records enqueued, payload bytes) — (0,0) if the conn is gone.
-    std::pair<int64_t, int64_t> send_ring(int64_t id, const uint8_t* ring, size_t wpos) {
+    // `ref` / `ref_len`: the reference buffer by-reference records point
+    // into (nullptr = none; see build_ring_frames).
+    std::pair<int64_t, int64_t> send_ring(int64_t id, const uint8_t* ring, size_t wpos,
+                                          const uint8_t* ref = nullptr, size_t ref_len = 0) {
         std::string buf;
-        auto r = build_ring_frames(ring, wpos, &buf);
+        auto r = build_ring_frames(ring, wpos, &buf, ref, ref_len);
         std::lock_guard<std::mutex> g(mu_);
         auto it = conns_.find(id);
         if (it == conns_.end() || it->second.closed || it->second.soft_closing)
@@ -253,14 +256,17 @@ public:
     std::vector<int64_t> send_rings_batch(const uint8_t* base,
                                           const std::vector<int64_t>& ids,
                                           const std::vector<int64_t>& starts,
-                                          const std::vector<int64_t>& ends) {
+                                          const std::vector<int64_t>& ends,
+                                          const uint8_t* ref = nullptr,
+                                          size_t ref_len = 0) {
         size_t n_users = ids.size();
         std::vector<int64_t> counts(n_users, 0);
         std::vector<std::string> bufs(n_users);
         std::vector<int64_t> payload(n_users, 0);
         for (size_t j = 0; j < n_users; ++j) {
             auto r = build_ring_frames(base + starts[j],
-                                       (size_t)(ends[j] - starts[j]), &bufs[j]);
+                                       (size_t)(ends[j] - starts[j]), &bufs[j],
+                                       ref, ref_len);
             counts[j] = r.first;
             payload[j] = r.second;
         }
@@ -468,23 +474,45 @@ private:
     // (gpu_engine.parse_ring_records).  Broadcast-only rings are already
     // in order, so the common case skips the sort entirely.  No lock
     // needed: reads caller memory, writes caller-owned `out`.
+    //
+    // By-reference records ({u32 len | kRefFlag, u32 seq, u64 ref_off}, no
+    // payload in the ring; gpu_engine.py "by-reference delivery") take
+    // their frame body from ref + ref_off.  One whose range leaves
+    // [0, ref_len) ends parsing like a malformed inline record; without a
+    // reference buffer the inline length check already stops at the flag.
+    static constexpr uint32_t kRefFlag = 0x80000000u;
     static std::pair<int64_t, int64_t> build_ring_frames(const uint8_t* ring, size_t wpos,
-                                                         std::string* out) {
+                                                         std::string* out,
+                                                         const uint8_t* ref = nullptr,
+                                                         size_t ref_len = 0) {
         int64_t n = 0, payload_bytes = 0;
         size_t pos = 0;
-        std::vector<std::pair<uint32_t, std::pair<size_t, uint32_t>>> recs;  // seq -> (off, len)
+        std::vector<std::pair<uint32_t, std::pair<const uint8_t*, uint32_t>>> recs;  // seq -> (src, len)
         bool ordered = true;
         while (pos + 16 <= wpos) {
             uint32_t len, seq;
             memcpy(&len, ring + pos, 4);
             memcpy(&seq, ring + pos + 4, 4);
-            if (len > kMaxMessageSize || pos + 16 + len > wpos) break;
+            const uint8_t* src;
+            size_t stride;
+            if (ref != nullptr && (len & kRefFlag)) {
+                len &= ~kRefFlag;
+                uint64_t ref_off;
+                memcpy(&ref_off, ring + pos + 8, 8);
+                if (len > kMaxMessageSize || ref_off > ref_len || len > ref_len - ref_off) break;
+                src = ref + ref_off;
+                stride = 16;
+            } else {
+                if (len > kMaxMessageSize || pos + 16 + len > wpos) break;
+                src = ring + pos + 16;
+                stride = 16 + (((size_t)len + 15) & ~(size_t)15);
+            }
             if (!recs.empty() && (uint32_t)(seq - recs.back().first) > 0x80000000u)
                 ordered = false;
-            recs.push_back({seq, {pos + 16, len}});
+            recs.push_back({seq, {src, len}});
             ++n;
             payload_bytes += (int64_t)len;
-            pos += 16 + (((size_t)len + 15) & ~(size_t)15);
+            pos += stride;
         }
         if (!ordered && recs.size() > 1) {
             uint32_t base = recs[0].first;
@@ -500,7 +528,7 @@ private:
             for (auto& r : recs) {
                 uint32_t be = htonl(r.second.second);
                 memcpy(&(*out)[w], &be, 4);
-                memcpy(&(*out)[w + 4], ring + r.second.first, r.second.second);
+                memcpy(&(*out)[w + 4], r.second.first, r.second.second);
                 w += 4 + r.second.second;
             }
         }

@@ -23,6 +23,12 @@ Delivery record format in a ring: {u32 len, u32 seq, u64 pad} + payload,
 16-byte aligned.  A drain (the socket-write analog) reads the cursors back,
 consumes records, and resets the cursors.
 
+By-reference delivery (ref_threshold set): a message of at least
+ref_threshold wire bytes is delivered as a bare 16-byte record
+{u32 len | 0x80000000, u32 seq, u64 ref_off}; its bytes stay in the host
+batch, which the engine retains and drain_compact_ref() hands back as the
+reference buffer ref_off indexes.
+
 CPU mode (device="cpu") runs the pure-Python mirrors from ops.reference so
 the engine's semantics are testable without a GPU.
 """
@@ -42,6 +48,7 @@ from ..utils.log import get_logger
 log = get_logger("gpu-engine")
 
 RING_ALIGN = 16
+REF_FLAG = 0x80000000  # top bit of a record's len word: by-reference record
 
 
 def ring_rec(length: int) -> int:
@@ -75,6 +82,7 @@ class GpuBrokerEngine:
         direct_enabled: bool = True,
         hash_seed: int = 0,
         n_peer_slots: int = 0,
+        ref_threshold: Optional[int] = None,
     ) -> None:
         # n_peer_slots (P): peer brokers as recipients of the device
         # pipeline.  The recipient index space is R = n_users + P; peer slot
@@ -143,6 +151,21 @@ class GpuBrokerEngine:
         # value (apply_direct_updates deletes); cleared by every rebuild
         self._direct_tombstones: set = set()
         self._direct_failed = torch.zeros(1, dtype=torch.int32, device=dev)
+        # by-reference delivery (None = off: exactly the inline kernels).
+        # Needs fanout_wire, so that host and device both know a message's
+        # fanned-out length from the batch offsets alone; every message
+        # that stays inline must fit an empty ring.
+        if ref_threshold is not None:
+            assert fanout_wire, "ref_threshold requires fanout_wire=True"
+            assert 1 <= ref_threshold < REF_FLAG
+            assert ring_rec(ref_threshold - 1) <= ring_bytes, (
+                f"ref_threshold {ref_threshold}: an inline message just below it "
+                f"does not fit a {ring_bytes}-byte ring")
+        self.ref_threshold = ref_threshold
+        # host batches that undrained by-reference records point into, in
+        # tick order, and their total size (the next batch's ref_base)
+        self._ref_batches: List[bytes] = []
+        self._ref_base = 0
         self.seq = 0
         self.total = TickStats()
         self._staging_dev: Optional[torch.Tensor] = None
@@ -437,11 +460,35 @@ class GpuBrokerEngine:
 
         origin: per-message int32 [M] tensor or list, 0 = from a local user,
         1 = from a peer broker (None = all local).  Remote-origin messages
-        never reach a peer ring (single hop)."""
+        never reach a peer ring (single hop).
+
+        With a ref_threshold, host_batch and host_offsets are required on
+        both engines: a batch that holds a by-reference message is retained
+        until the next drain."""
+        ref_base = 0
+        if self.ref_threshold is not None:
+            if host_batch is None or host_offsets is None:
+                raise ValueError("by-reference delivery needs host_batch and host_offsets")
+            ref_base = self._retain_batch(host_batch, host_offsets)
         if self.use_gpu_ops:
-            return self._tick_gpu(buf, offsets, uniform_wire_len, origin)
+            return self._tick_gpu(buf, offsets, uniform_wire_len, origin, ref_base)
         assert host_batch is not None and host_offsets is not None
-        return self._tick_cpu(host_batch, host_offsets, origin)
+        return self._tick_cpu(host_batch, host_offsets, origin, ref_base)
+
+    def _retain_batch(self, host_batch, host_offsets) -> int:
+        """Keep `host_batch` for the next drain if any of its messages goes
+        by reference.  Returns the batch's offset in the reference buffer."""
+        thr = self.ref_threshold
+        base = self._ref_base
+        if any(host_offsets[i + 1] - host_offsets[i] >= thr
+               for i in range(len(host_offsets) - 1)):
+            self._ref_batches.append(host_batch)
+            self._ref_base = base + len(host_batch)
+        return base
+
+    def _discard_ref_batches(self) -> None:
+        self._ref_batches = []
+        self._ref_base = 0
 
     def _k2b_block_scratch(self, M: int):
         """Lazily (re)allocate the block-K2b scratch for batches up to M
@@ -480,7 +527,8 @@ class GpuBrokerEngine:
             )
 
     def _tick_gpu(self, buf: torch.Tensor, offsets: torch.Tensor,
-                  uniform_wire_len: Optional[int] = None, origin=None) -> TickStats:
+                  uniform_wire_len: Optional[int] = None, origin=None,
+                  ref_base: int = 0) -> TickStats:
         ops = self._ops
         M = offsets.shape[0] - 1
         disc, payload_off, payload_len, topics_off, topics_cnt, recip_hash, _ts = ops.parse_batch(
@@ -504,8 +552,18 @@ class GpuBrokerEngine:
         # count stays on device
         self._n_pairs.zero_()
         uniform = self.fanout_wire and uniform_wire_len is not None
+        thr = self.ref_threshold
+        # ring_len: what K2b / K5b claim ring space for — 0 (a bare header)
+        # for a by-reference message.  A uniform length at or above the
+        # threshold leaves the flat path: its records are headers only.
+        ring_len = payload_len
+        if thr is not None:
+            if uniform and uniform_wire_len >= thr:
+                uniform = False
+            if not uniform:
+                ring_len = torch.where(payload_len >= thr, 0, payload_len).to(torch.int32)
         rec = ring_rec(uniform_wire_len) if uniform else 0
-        self._assign_emit(ops, mask_t, payload_len, rec, M)
+        self._assign_emit(ops, mask_t, ring_len, rec, M)
         if self.direct_enabled:
             # K5 lookup + K5b on-device delivery-pair emission: direct pairs
             # append to the same pair list, all consumed by the single
@@ -514,12 +572,12 @@ class GpuBrokerEngine:
             # same padded wire length as broadcasts.)
             owner = ops.direct_lookup(self.direct_keys, self.direct_vals, recip_hash)
             if peer_plane:
-                ops.emit_direct_peers(disc, owner, origin, payload_off, payload_len,
+                ops.emit_direct_peers(disc, owner, origin, payload_off, ring_len,
                                       self.ring_bytes, self.n_users, self.n_peer_slots,
                                       self.ring_wpos, self._n_pairs, self._pairs,
                                       self._drops)
             else:
-                ops.emit_direct(disc, owner, payload_off, payload_len, self.ring_bytes,
+                ops.emit_direct(disc, owner, payload_off, ring_len, self.ring_bytes,
                                 self.ring_wpos, self._n_pairs, self._pairs, self._drops)
         seq_base = self.seq
         self.seq += M
@@ -537,8 +595,12 @@ class GpuBrokerEngine:
                              uniform_wire_len)
         else:
             seq = torch.arange(seq_base, seq_base + M, dtype=torch.int32, device=self.device)
-            ops.fanout_wave(buf, payload_off, payload_len, self._pairs, seq,
-                            self._n_pairs, self.egress, nt, 0)
+            if thr is not None:
+                ops.fanout_ref(buf, payload_off, payload_len, self._pairs, seq,
+                               self._n_pairs, self.egress, nt, 0, thr, ref_base)
+            else:
+                ops.fanout_wave(buf, payload_off, payload_len, self._pairs, seq,
+                                self._n_pairs, self.egress, nt, 0)
         return TickStats(n_messages=M)
 
     def _graph_tick_body(self, buf: torch.Tensor, offsets: torch.Tensor, units: int) -> None:
@@ -568,6 +630,10 @@ class GpuBrokerEngine:
         ~8 kernel launches). Requires fanout_wire + uniform records +
         direct_enabled=False (the broadcast-bench shape)."""
         assert self.fanout_wire and not self.direct_enabled
+        if self.ref_threshold is not None and uniform_wire_len >= self.ref_threshold:
+            raise ValueError("tick_graphed carries inline records only: "
+                             f"wire length {uniform_wire_len} is at or above "
+                             f"ref_threshold {self.ref_threshold}")
         units = ring_rec(uniform_wire_len) // 16
         key = (buf.data_ptr(), offsets.data_ptr(), units)
         g = self._graphs.get(key)
@@ -591,7 +657,8 @@ class GpuBrokerEngine:
             self._graphs[key] = g
         g.replay()
 
-    def _tick_cpu(self, batch: bytes, offsets: List[int], origin=None) -> TickStats:
+    def _tick_cpu(self, batch: bytes, offsets: List[int], origin=None,
+                  ref_base: int = 0) -> TickStats:
         from ..ops import reference as ref
 
         pr = ref.parse_batch(batch, offsets, self.hash_seed)
@@ -605,20 +672,31 @@ class GpuBrokerEngine:
                 torch.tensor(offsets[1:], dtype=torch.int64)
                 - torch.tensor(offsets[:-1], dtype=torch.int64)
             ).to(torch.int32)
+        thr = self.ref_threshold
+        ring_len = pr.payload_len if thr is None else ref.ring_lengths(pr.payload_len, thr)
+
+        def fan(p_user, p_msg, p_dst):
+            if thr is None:
+                ref.fanout(batch, pr.payload_off, pr.payload_len, p_user, p_msg, p_dst,
+                           seq, arr)
+            else:
+                ref.fanout_ref(batch, pr.payload_off, pr.payload_len, p_user, p_msg, p_dst,
+                               seq, arr, thr, ref_base)
+
         pair_user, pair_msg, pair_dst, drops = ref.assign_emit(
-            mask, pr.payload_len, self.ring_wpos, self.ring_bytes, self.n_recipients
+            mask, ring_len, self.ring_wpos, self.ring_bytes, self.n_recipients
         )
         seq = torch.arange(self.seq, self.seq + M, dtype=torch.int32)
         self.seq += M
         arr = bytearray(self.egress.numpy().tobytes())  # copy-in; copied back below
-        ref.fanout(batch, pr.payload_off, pr.payload_len, pair_user, pair_msg, pair_dst, seq, arr)
+        fan(pair_user, pair_msg, pair_dst)
         # Direct deliveries claim ring space after the broadcasts, in message
         # order: local users and, for local-origin messages, peer slots
         owner = ref.direct_lookup(self.direct_keys, self.direct_vals, pr.recip_hash)
         d_user, d_msg, d_dst, d_drops = ref.emit_direct_peers(
-            pr.disc, owner, origin, pr.payload_len, self.ring_wpos, self.ring_bytes,
+            pr.disc, owner, origin, ring_len, self.ring_wpos, self.ring_bytes,
             self.n_users, self.n_peer_slots)
-        ref.fanout(batch, pr.payload_off, pr.payload_len, d_user, d_msg, d_dst, seq, arr)
+        fan(d_user, d_msg, d_dst)
         self.egress.copy_(torch.frombuffer(arr, dtype=torch.uint8))
         return TickStats(n_messages=M, n_deliveries=int(pair_user.shape[0]),
                          n_drops=drops + d_drops)
@@ -626,7 +704,10 @@ class GpuBrokerEngine:
     # ------------------------------- drain ---------------------------------
 
     def drain_cursors(self) -> torch.Tensor:
-        """Read back ring cursors (the per-tick notify) and reset them."""
+        """Read back ring cursors (the per-tick notify) and reset them.
+        Retained by-reference batches are discarded: the cursors were the
+        only way to reach the records that point into them."""
+        self._discard_ref_batches()
         wpos = self.ring_wpos.detach().clone().to("cpu")
         self.ring_wpos.zero_()
         return wpos
@@ -639,9 +720,29 @@ class GpuBrokerEngine:
         (wpos[N] cpu, offsets[N+1] cpu, staging host uint8) where user u's
         records occupy staging[offsets[u]:offsets[u+1]].  Reference analog:
         the Arc-clone fan-out never copies per recipient either
-        (user/sender.rs:16-33)."""
+        (user/sender.rs:16-33).  Retained by-reference batches are discarded
+        (use drain_compact_ref to get them)."""
+        self._discard_ref_batches()
+        return self._drain_compact()
+
+    def drain_compact_ref(self):
+        """drain_compact plus the reference buffer: returns (wpos, offsets,
+        staging, refbuf).  A by-reference record's ref_off indexes refbuf:
+        the retained host batch itself when the drain covers one (no copy),
+        the retained batches joined in tick order otherwise, b"" when
+        nothing went by reference.  Clears the retained batches."""
+        batches = self._ref_batches
+        self._discard_ref_batches()
+        if len(batches) == 1:
+            refbuf = batches[0]
+        else:
+            refbuf = b"".join(bytes(b) for b in batches)
+        return (*self._drain_compact(), refbuf)
+
+    def _drain_compact(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         if not self.use_gpu_ops:
-            wpos = self.drain_cursors()
+            wpos = self.ring_wpos.detach().clone()
+            self.ring_wpos.zero_()
             offsets = torch.zeros(self.n_recipients + 1, dtype=torch.int64)
             torch.cumsum(wpos, 0, out=offsets[1:])
             total = int(offsets[-1])
@@ -695,9 +796,13 @@ class GpuBrokerEngine:
         return bytes(self.egress[start : start + n].to("cpu").numpy().tobytes())
 
 
-def parse_ring_records(ring: bytes, wpos: int) -> List[Tuple[int, bytes]]:
+def parse_ring_records(ring: bytes, wpos: int, refbuf=None) -> List[Tuple[int, bytes]]:
     """Parse delivery records out of a drained ring, ordered by sequence
     number: [(seq, payload), ...].
+
+    A by-reference record (REF_FLAG set in its len word, no payload in the
+    ring) resolves to refbuf[ref_off : ref_off + len]; without a refbuf, or
+    with a range outside it, it raises ValueError.
 
     Ring WRITE order is claim order: broadcasts are per-user ordered by
     K2b, but K5b's direct-delivery claims are atomic and may interleave
@@ -710,6 +815,18 @@ def parse_ring_records(ring: bytes, wpos: int) -> List[Tuple[int, bytes]]:
     while pos + 16 <= wpos:
         length = int.from_bytes(ring[pos : pos + 4], "little")
         seq = int.from_bytes(ring[pos + 4 : pos + 8], "little")
+        if length & REF_FLAG:
+            length &= REF_FLAG - 1
+            ref_off = int.from_bytes(ring[pos + 8 : pos + 16], "little")
+            if refbuf is None:
+                raise ValueError("by-reference record without a reference buffer")
+            if ref_off + length > len(refbuf):
+                raise ValueError(
+                    f"by-reference record [{ref_off}, {ref_off + length}) outside "
+                    f"the {len(refbuf)}-byte reference buffer")
+            out.append((seq, bytes(refbuf[ref_off : ref_off + length])))
+            pos += RING_ALIGN
+            continue
         payload = ring[pos + 16 : pos + 16 + length]
         out.append((seq, payload))
         pos += ring_rec(length)

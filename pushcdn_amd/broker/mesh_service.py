@@ -69,6 +69,8 @@ class MeshBroker(Broker):
     BLOB_INGEST = True
     # the broker plane is the collective: no device peer rings here
     PEER_FORWARD = False
+    # the collective tick delivers inline records only
+    REF_DELIVERY = False
 
     def __init__(self, config: BrokerConfig, batch_capacity: int = 1 << 22,
                  interest_routed: Optional[bool] = None) -> None:

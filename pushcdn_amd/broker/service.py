@@ -104,6 +104,12 @@ class BrokerConfig:
     gpu_peer_forward: bool = False
     gpu_max_peers: int = 32
     gpu_direct_table_size: int = 1 << 16
+    # by-reference delivery on the GPU plane: a message of at least this
+    # many wire bytes takes a 16-byte record in each recipient's ring and
+    # its bytes go out from the tick's single host copy (no per-recipient
+    # HBM write, no D2H of the payload, no ring-size limit on the message).
+    # None: every delivery is copied into the ring, as before.
+    gpu_ref_threshold: Optional[int] = None
 
 
 @dataclass
@@ -123,6 +129,10 @@ class Broker:
     # MeshBroker overrides to False: its broker plane is the collective,
     # so config.gpu_peer_forward has no effect there
     PEER_FORWARD = True
+    # MeshBroker overrides to False as well: its tick drives the engine
+    # through the collective path, which delivers inline records only, so
+    # config.gpu_ref_threshold has no effect there
+    REF_DELIVERY = True
 
     def __init__(self, config: BrokerConfig) -> None:
         from ..proto.transports.tcp import Tcp
@@ -153,6 +163,9 @@ class Broker:
         self._peer_slot_of: Dict[BrokerIdentifier, int] = {}
         self._free_peer_slots: List[int] = []
         self._peer_slots_exhausted_logged = False
+        self._ref_threshold = (config.gpu_ref_threshold
+                               if config.data_plane == "gpu" and type(self).REF_DELIVERY
+                               else None)
         if config.data_plane == "gpu":
             from .gpu_engine import GpuBrokerEngine
 
@@ -167,6 +180,7 @@ class Broker:
                 direct_table_size=config.gpu_direct_table_size,
                 n_peer_slots=n_peer_slots,
                 fanout_wire=True,  # forward raw wire bytes verbatim
+                ref_threshold=self._ref_threshold,
                 # keyed routing hash: cluster-wide secret derived from the
                 # shared broker private key (see keyhash.derive_routing_seed)
                 hash_seed=derive_routing_seed(self.keypair.private_key),
@@ -864,7 +878,13 @@ class Broker:
                 # a failed dispatch (e.g. eviction errors) must not kill the
                 # tick loop; the buffer is no longer being written either way
                 pass
-        wpos, offsets, staging = self._engine.drain_compact()
+        # refbuf: the host batch this tick's by-reference records point
+        # into; the dispatch closure keeps it alive until its sends are queued
+        if self._ref_threshold is not None:
+            wpos, offsets, staging, refbuf = self._engine.drain_compact_ref()
+        else:
+            wpos, offsets, staging = self._engine.drain_compact()
+            refbuf = None
         # who owns each peer ring is fixed NOW, with the cursors: the
         # dispatch runs later, and a slot released and re-claimed in between
         # must not hand this tick's bytes to its new occupant
@@ -878,15 +898,17 @@ class Broker:
                     await asyncio.shield(prev)
                 except Exception:
                     pass
-            await self._dispatch_egress(wpos, offsets, staging, peers)
+            await self._dispatch_egress(wpos, offsets, staging, peers, refbuf)
 
         task = asyncio.get_running_loop().create_task(_dispatch_chained())
         self._drain_by_buffer[idx] = task
         self._last_drain = task
 
-    async def _dispatch_egress(self, wpos, offsets, staging, peers=()) -> None:
+    async def _dispatch_egress(self, wpos, offsets, staging, peers=(),
+                               refbuf=None) -> None:
         """`peers`: [(broker, peer slot, handle)] as of the drain that
-        produced wpos/offsets/staging."""
+        produced wpos/offsets/staging.  `refbuf`: that drain's reference
+        buffer (drain_compact_ref), None when by-reference delivery is off."""
         from .gpu_engine import parse_ring_records
 
         by_pump = {}        # pump -> [(pubkey, cid, start, end)]
@@ -945,8 +967,12 @@ class Broker:
                 per = (len(entries) + nshards - 1) // nshards
                 for i in range(0, len(entries), per):
                     chunk = entries[i:i + per]
+                    if refbuf is not None:
+                        call = (pump.send_rings_batch_ref, view, refbuf)
+                    else:
+                        call = (pump.send_rings_batch, view)
                     jobs.append((chunk, loop.run_in_executor(
-                        None, pump.send_rings_batch, view,
+                        None, *call,
                         [e[1] for e in chunk],
                         [e[2] for e in chunk],
                         [e[3] for e in chunk],
@@ -971,20 +997,20 @@ class Broker:
                          .tobytes())
             if self.connections.brokers.get(broker) is not handle:
                 continue
-            sink = getattr(handle.connection, "send_ring_records", None)
+            sink = self._ring_sink(handle.connection, refbuf)
             if sink is not None:
                 try:
                     sink(ring, n)
                 except Exception:
                     await self.remove_broker(broker)
             else:
-                for _seq, payload in parse_ring_records(ring, n):
+                for _seq, payload in parse_ring_records(ring, n, refbuf):
                     await self.try_send_to_broker(broker, Bytes(payload))
         for slot, pubkey, n in fallback:
             ring = bytes(staging[int(offsets[slot]):int(offsets[slot + 1])].numpy()
                          .tobytes())
             handle = self.connections.users.get(pubkey)
-            sink = getattr(handle.connection, "send_ring_records", None) \
+            sink = self._ring_sink(handle.connection, refbuf) \
                 if handle is not None else None
             if sink is not None:
                 try:
@@ -992,8 +1018,19 @@ class Broker:
                 except Exception:
                     await self.remove_user(pubkey)
             else:
-                for _seq, payload in parse_ring_records(ring, n):
+                for _seq, payload in parse_ring_records(ring, n, refbuf):
                     await self.try_send_to_user(pubkey, Bytes(payload))
+
+    @staticmethod
+    def _ring_sink(connection, refbuf):
+        """The connection's native ring sender, bound to `refbuf` when the
+        drain carries by-reference records; None = parse in Python."""
+        if refbuf is None:
+            return getattr(connection, "send_ring_records", None)
+        sink = getattr(connection, "send_ring_records_ref", None)
+        if sink is None:
+            return None
+        return lambda ring, n: sink(ring, n, refbuf)
 
     async def _forward_to_mesh(self, raw: Bytes, fwd) -> None:
         """Broker-plane forwarding for a LOCAL-origin message on the GPU
@@ -1093,7 +1130,12 @@ class Broker:
             # ingest staging from the bounded HBM pool: exhaustion WAITS
             # here (backpressure up through the tick queue to the sockets),
             # matching the reference limiter (protocols/mod.rs:328)
-            pb = await self._hbm_pool.alloc(len(buf)) if self._hbm_pool else None
+            # A tick larger than the whole pool could never be granted
+            # (alloc raises, which would end this task and the broker with
+            # it): such a tick is ingested without pool staging.
+            pool = self._hbm_pool
+            pb = await pool.alloc(len(buf)) \
+                if pool is not None and len(buf) <= pool.capacity else None
             host = bytes(buf)
             if origin is None:
                 dbuf, doff = self._engine.ingest(

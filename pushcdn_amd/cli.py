@@ -57,6 +57,10 @@ def _broker_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--global-memory-pool-size", type=int, default=1 << 30)
     p.add_argument("--data-plane", choices=["host", "gpu"], default="host")
     p.add_argument("--gpu-device", default="cuda:0")
+    p.add_argument("--gpu-ref-threshold", type=int, default=None,
+                   help="GPU data plane: deliver messages of at least this many wire "
+                        "bytes by reference (16-byte ring record, bytes sent from the "
+                        "host copy); unset = every delivery copied into the ring")
     p.add_argument("--user-transport", choices=["tcp", "tcp-tls", "tcp-native", "quic", "quic-native"],
                    default="tcp", help="user-plane transport (tcp-native = C++ epoll "
                                        "pump; quic[-native] = QUIC-profile over UDP)")
@@ -80,6 +84,7 @@ def cmd_broker(args) -> None:
         ca_key_path=args.ca_key_path,
         data_plane=args.data_plane,
         gpu_device=args.gpu_device,
+        gpu_ref_threshold=args.gpu_ref_threshold,
         user_protocol=_transport(args.user_transport),
         broker_protocol=_transport(args.broker_transport),
     )

@@ -17,7 +17,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from ..utils.keyhash import fnv1a64
-from ..broker.gpu_engine import ring_rec
+from ..broker.gpu_engine import REF_FLAG, ring_rec
 
 
 @dataclass
@@ -251,6 +251,47 @@ def fanout(
         egress[dst + 16 : dst + 16 + length] = buf[off : off + length]
         if zero_pad_to is not None and zero_pad_to > 16 + length:
             egress[dst + 16 + length : dst + zero_pad_to] = bytes(zero_pad_to - 16 - length)
+
+
+def ring_lengths(payload_len: torch.Tensor, ref_threshold: int) -> torch.Tensor:
+    """The by-reference ring-length split: the length K2b / K5b claim ring
+    space for.  A message of at least ref_threshold bytes takes a bare
+    header (length 0 -> ring_rec(0) = 16 B); a shorter one its own length."""
+    return torch.where(payload_len >= ref_threshold,
+                       torch.zeros_like(payload_len), payload_len)
+
+
+def fanout_ref(
+    buf: bytes,
+    payload_off: torch.Tensor,
+    payload_len: torch.Tensor,
+    pair_user: torch.Tensor,
+    pair_msg: torch.Tensor,
+    pair_dst: torch.Tensor,
+    msg_seq: torch.Tensor,
+    egress: bytearray,
+    ref_threshold: int,
+    ref_base: int,
+) -> None:
+    """Mirror of k3_fanout_ref: a pair whose message is shorter than
+    ref_threshold is written exactly as fanout writes it; any other gets the
+    16 B header {u32 len | REF_FLAG, u32 seq, u64 ref_base + payload_off}
+    and nothing else."""
+    import struct
+
+    for p in range(pair_user.shape[0]):
+        u = int(pair_user[p])
+        if u < 0:
+            continue
+        m = int(pair_msg[p])
+        off, length = int(payload_off[m]), int(payload_len[m])
+        dst = int(pair_dst[p])
+        seq = int(msg_seq[m]) & 0xFFFFFFFF
+        if length >= ref_threshold:
+            struct.pack_into("<IIQ", egress, dst, length | REF_FLAG, seq, ref_base + off)
+            continue
+        struct.pack_into("<IIII", egress, dst, length, seq, 0, 0)
+        egress[dst + 16 : dst + 16 + length] = buf[off : off + length]
 
 
 def apply_subs(

@@ -232,6 +232,16 @@ class PumpConnection(Connection):
             BYTES_SENT.inc(payload_bytes)
         return n
 
+    def send_ring_records_ref(self, ring: bytes, wpos: int, refbuf) -> int:
+        """send_ring_records for a ring that may hold by-reference records:
+        the pump copies their frame bodies out of `refbuf`."""
+        if self._closed or self._dead:
+            raise ConnectionError_("connection writer closed")
+        n, payload_bytes = self._pump.send_ring_ref(self._cid, ring, wpos, refbuf)
+        if payload_bytes:
+            BYTES_SENT.inc(payload_bytes)
+        return n
+
     async def soft_close(self) -> None:
         if self._closed:
             return
