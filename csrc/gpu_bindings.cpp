@@ -1,6 +1,7 @@
 // Torch extension bindings for the MI355X broker data-plane kernels
 // (csrc/hip/dataplane.hip). PyTorch owns every HBM buffer; these calls
-// invoke the extern "C" launchers defined next to the kernels.
+// invoke the extern "C" launchers defined next to the kernels and declared
+// in csrc/hip/dataplane.h and csrc/hip/bls_kernels.h.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -8,79 +9,8 @@
 
 #include <cstdint>
 
-struct ParseOut {
-    int32_t* disc;
-    int64_t* payload_off;
-    int32_t* payload_len;
-    int64_t* topics_off;
-    int32_t* topics_cnt;
-    uint64_t* recip_hash;
-    uint64_t* timestamp;
-};
-
-struct alignas(16) PairRec { int32_t user; int32_t msg; int64_t dst; };
-
-extern "C" {
-void launch_k4_parse(const uint8_t*, const int64_t*, int32_t, uint64_t, ParseOut, hipStream_t);
-void launch_k2a_topic_mask(const uint64_t*, const uint8_t*, const int64_t*, const int32_t*,
-                           const int32_t*, uint64_t*, int32_t, int32_t, hipStream_t);
-void launch_k2b_count(const uint64_t*, int32_t, int32_t, int32_t, int32_t*, hipStream_t);
-void launch_k2b_emit(const uint64_t*, const int64_t*, const int32_t*, const int32_t*, int32_t,
-                     int32_t, int32_t, int64_t, uint64_t*, PairRec*, uint32_t*, hipStream_t);
-void launch_k3_fanout(const uint8_t*, const int64_t*, const int32_t*, const PairRec*,
-                      const uint32_t*, int32_t, uint8_t*, hipStream_t);
-void launch_k5_direct_lookup(const uint64_t*, const int32_t*, int64_t, const uint64_t*, int32_t,
-                             int32_t*, hipStream_t);
-void launch_k2c_apply_subs(uint64_t*, const uint8_t*, const int64_t*, const int32_t*,
-                           const int32_t*, const int32_t*, int32_t, int32_t, hipStream_t);
-void launch_k1_bls_verify(const uint8_t*, const uint8_t*, uint8_t*, const int64_t*, int32_t,
-                          int32_t*, hipStream_t);
-void launch_k1_hash_to_g1(uint8_t*, const int64_t*, int32_t, uint8_t*, hipStream_t);
-void launch_k1_precompute_g2_lines(uint8_t*, int32_t*, hipStream_t);
-void launch_k7_compact_rings(const uint8_t*, int64_t, const int64_t*, const int64_t*,
-                             uint8_t*, int32_t, int32_t, hipStream_t);
-void launch_k1_bls_verify2(const uint8_t*, const uint8_t*, uint8_t*, const int64_t*,
-                           const uint8_t*, int32_t, int32_t*, hipStream_t);
-void launch_k1_bls_verify_wave(const uint8_t*, const uint8_t*, uint8_t*, const int64_t*,
-                               const uint8_t*, const uint64_t*, int32_t, int32_t*,
-                               hipStream_t);
-void launch_k1_dbg_wave(const uint8_t*, const uint8_t*, uint8_t*, const int64_t*,
-                        const uint8_t*, const uint64_t*, int32_t, int32_t, int32_t*,
-                        hipStream_t);
-void launch_k3_fanout_ref(const uint8_t*, const int64_t*, const int32_t*, const PairRec*,
-                          const uint32_t*, const int32_t*, int32_t, int32_t, int64_t,
-                          uint8_t*, int, int, hipStream_t);
-void launch_k3_fanout_wave(const uint8_t*, const int64_t*, const int32_t*, const PairRec*,
-                           const uint32_t*, const int32_t*, int32_t, uint8_t*, int, int,
-                           hipStream_t);
-void launch_k3_fanout_flat2(const uint8_t*, const int64_t*, const int32_t*, const PairRec*,
-                            uint32_t, const int32_t*, int32_t, int32_t, int32_t, uint8_t*,
-                            int, int, hipStream_t);
-void launch_k3_fanout_flat3(const uint8_t*, const int64_t*, const int32_t*, const PairRec*,
-                            const uint32_t*, const int32_t*, int32_t, int32_t, int32_t,
-                            uint8_t*, int, int, hipStream_t);
-void launch_k_seq_advance(uint32_t*, int32_t, hipStream_t);
-void launch_k5b_emit_direct(const int32_t*, const int32_t*, const int64_t*, const int32_t*,
-                            int32_t, int64_t, int32_t, uint64_t*, int32_t*, PairRec*,
-                            uint32_t*, hipStream_t);
-void launch_k2a_topic_mask_t(const uint64_t*, const uint8_t*, const int64_t*, const int32_t*,
-                             const int32_t*, uint64_t*, int32_t, int32_t, hipStream_t);
-void launch_k2b_fused_t(const uint64_t*, const int32_t*, int32_t, int32_t, int32_t, int64_t,
-                        int32_t, int32_t, uint64_t*, int32_t*, PairRec*, uint32_t*,
-                        hipStream_t);
-void launch_k2b_blocks_t(const uint64_t*, int32_t, int32_t, int32_t, int64_t, int32_t,
-                         int32_t, uint64_t*, int32_t*, int32_t*, int32_t*, int32_t*,
-                         int32_t*, int64_t*, PairRec*, uint32_t*, hipStream_t);
-void launch_k2a_topic_mask_origin_t(const uint64_t*, const uint8_t*, const int64_t*,
-                                    const int32_t*, const int32_t*, const int32_t*, uint64_t*,
-                                    int32_t, int32_t, int32_t, hipStream_t);
-void launch_k5b_emit_direct_peers(const int32_t*, const int32_t*, const int32_t*,
-                                  const int64_t*, const int32_t*, int32_t, int32_t, int32_t,
-                                  int64_t, int32_t, uint64_t*, int32_t*, PairRec*, uint32_t*,
-                                  hipStream_t);
-void launch_k6_direct_apply(uint64_t*, int32_t*, int64_t, const uint64_t*, const int32_t*,
-                            int32_t, const uint64_t*, int32_t, uint32_t*, hipStream_t);
-}
+#include "hip/bls_kernels.h"
+#include "hip/dataplane.h"
 
 #define CHECK_DEV(x) TORCH_CHECK(x.is_cuda(), #x " must be on the GPU")
 #define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -93,6 +23,11 @@ static inline PairRec* pair_ptr(torch::Tensor& pairs) {
 
 static inline hipStream_t cur_stream() {
     return at::hip::getCurrentHIPStream().stream();
+}
+
+// Options for a new tensor of `dtype` on the device of `like`.
+static inline torch::TensorOptions opts(torch::ScalarType dtype, const torch::Tensor& like) {
+    return torch::TensorOptions().dtype(dtype).device(like.device());
 }
 
 // The flat K3 kernels index units with an exact u32 magic division
@@ -113,8 +48,8 @@ std::vector<torch::Tensor> parse_batch(torch::Tensor buf, torch::Tensor offsets,
     TORCH_CHECK(buf.dtype() == torch::kUInt8 && offsets.dtype() == torch::kInt64);
     int32_t M = (int32_t)offsets.size(0) - 1;
     TORCH_CHECK(M >= 0);
-    auto o32 = torch::TensorOptions().dtype(torch::kInt32).device(buf.device());
-    auto o64 = torch::TensorOptions().dtype(torch::kInt64).device(buf.device());
+    auto o32 = opts(torch::kInt32, buf);
+    auto o64 = opts(torch::kInt64, buf);
     auto disc = torch::empty({M}, o32);
     auto payload_off = torch::empty({M}, o64);
     auto payload_len = torch::empty({M}, o32);
@@ -134,21 +69,30 @@ std::vector<torch::Tensor> parse_batch(torch::Tensor buf, torch::Tensor offsets,
     return {disc, payload_off, payload_len, topics_off, topics_cnt, recip_hash, timestamp};
 }
 
+// Shared part of the three K2a wrappers: M and W from disc and the bitmap,
+// the mask allocation ([M][W], or [W][M] when transposed) and the M > 0
+// guard around launch(mask, M, W).  Each wrapper does its own checks first.
+template <typename Launch>
+static torch::Tensor k2a_mask(const torch::Tensor& sub_bitmap, const torch::Tensor& buf,
+                              const torch::Tensor& disc, bool transposed, Launch launch) {
+    int32_t W = (int32_t)sub_bitmap.size(1);
+    int32_t M = (int32_t)disc.size(0);
+    auto mask = transposed ? torch::empty({(int64_t)W, M}, opts(torch::kInt64, buf))
+                           : torch::empty({M, (int64_t)W}, opts(torch::kInt64, buf));
+    if (M > 0) launch((uint64_t*)mask.data_ptr<int64_t>(), M, W);
+    return mask;
+}
+
 torch::Tensor topic_mask(torch::Tensor sub_bitmap, torch::Tensor buf, torch::Tensor topics_off,
                          torch::Tensor topics_cnt, torch::Tensor disc) {
     CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap);
     TORCH_CHECK(sub_bitmap.dim() == 2 && sub_bitmap.size(0) == 256);
-    int32_t W = (int32_t)sub_bitmap.size(1);
-    int32_t M = (int32_t)disc.size(0);
-    auto mask = torch::empty({M, (int64_t)W},
-                             torch::TensorOptions().dtype(torch::kInt64).device(buf.device()));
-    if (M > 0) {
+    return k2a_mask(sub_bitmap, buf, disc, false, [&](uint64_t* mask, int32_t M, int32_t W) {
         launch_k2a_topic_mask((const uint64_t*)sub_bitmap.data_ptr<int64_t>(),
                               buf.data_ptr<uint8_t>(), topics_off.data_ptr<int64_t>(),
-                              topics_cnt.data_ptr<int32_t>(), disc.data_ptr<int32_t>(),
-                              (uint64_t*)mask.data_ptr<int64_t>(), M, W, cur_stream());
-    }
-    return mask;
+                              topics_cnt.data_ptr<int32_t>(), disc.data_ptr<int32_t>(), mask, M,
+                              W, cur_stream());
+    });
 }
 
 std::vector<torch::Tensor> assign_emit(torch::Tensor mask, torch::Tensor payload_off,
@@ -158,7 +102,7 @@ std::vector<torch::Tensor> assign_emit(torch::Tensor mask, torch::Tensor payload
     int32_t M = (int32_t)mask.size(0);
     int32_t W = (int32_t)mask.size(1);
     TORCH_CHECK(ring_bytes % 16 == 0, "ring_bytes must be a multiple of 16");
-    auto o32 = torch::TensorOptions().dtype(torch::kInt32).device(mask.device());
+    auto o32 = opts(torch::kInt32, mask);
     auto counts = torch::zeros({n_users}, o32);
     launch_k2b_count((const uint64_t*)mask.data_ptr<int64_t>(), M, W, (int32_t)n_users,
                      counts.data_ptr<int32_t>(), cur_stream());
@@ -184,8 +128,7 @@ void fanout(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor payload_
     CHECK_DEV(egress); CHECK_CONTIG(egress);
     int32_t n_pairs = (int32_t)pair_user.size(0);
     if (n_pairs == 0) return;
-    auto pairs = torch::empty({n_pairs, 4},
-                              torch::TensorOptions().dtype(torch::kInt32).device(buf.device()));
+    auto pairs = torch::empty({n_pairs, 4}, opts(torch::kInt32, buf));
     pairs.select(1, 0).copy_(pair_user);
     pairs.select(1, 1).copy_(pair_msg);
     pairs.slice(1, 2, 4).view(torch::kInt64).squeeze(1).copy_(pair_dst);
@@ -201,8 +144,7 @@ torch::Tensor direct_lookup(torch::Tensor table_keys, torch::Tensor table_vals,
     int64_t S = table_keys.size(0);
     TORCH_CHECK((S & (S - 1)) == 0, "table size must be a power of two");
     int32_t N = (int32_t)query.size(0);
-    auto owner = torch::empty({N},
-                              torch::TensorOptions().dtype(torch::kInt32).device(query.device()));
+    auto owner = torch::empty({N}, opts(torch::kInt32, query));
     if (N > 0) {
         launch_k5_direct_lookup((const uint64_t*)table_keys.data_ptr<int64_t>(),
                                 table_vals.data_ptr<int32_t>(), S,
@@ -230,7 +172,7 @@ torch::Tensor bls_verify_batch(torch::Tensor vks, torch::Tensor sigs, torch::Ten
     CHECK_CONTIG(vks); CHECK_CONTIG(sigs); CHECK_CONTIG(msgs); CHECK_CONTIG(moff);
     int32_t N = (int32_t)moff.size(0) - 1;
     TORCH_CHECK(vks.numel() == (int64_t)N * 128 && sigs.numel() == (int64_t)N * 64);
-    auto ok = torch::zeros({N}, torch::TensorOptions().dtype(torch::kInt32).device(vks.device()));
+    auto ok = torch::zeros({N}, opts(torch::kInt32, vks));
     if (N > 0) {
         launch_k1_bls_verify(vks.data_ptr<uint8_t>(), sigs.data_ptr<uint8_t>(),
                              msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(), N,
@@ -254,11 +196,8 @@ void compact_rings(torch::Tensor egress, int64_t ring_bytes, torch::Tensor wpos,
 torch::Tensor precompute_g2_lines(torch::Tensor device_probe) {
     // fixed-g2 Miller-loop line coefficients (128 records x 192 B); computed
     // once per process by a 1-thread kernel, consumed by bls_verify_batch2
-    auto out = torch::zeros({128 * 192},
-                            torch::TensorOptions().dtype(torch::kUInt8)
-                                .device(device_probe.device()));
-    auto n = torch::zeros({1}, torch::TensorOptions().dtype(torch::kInt32)
-                                   .device(device_probe.device()));
+    auto out = torch::zeros({128 * 192}, opts(torch::kUInt8, device_probe));
+    auto n = torch::zeros({1}, opts(torch::kInt32, device_probe));
     launch_k1_precompute_g2_lines(out.data_ptr<uint8_t>(), n.data_ptr<int32_t>(),
                                   cur_stream());
     return out;
@@ -271,7 +210,7 @@ torch::Tensor bls_verify_batch2(torch::Tensor vks, torch::Tensor sigs, torch::Te
     CHECK_CONTIG(g2_lines);
     int32_t N = (int32_t)moff.size(0) - 1;
     TORCH_CHECK(vks.numel() == (int64_t)N * 128 && sigs.numel() == (int64_t)N * 64);
-    auto ok = torch::zeros({N}, torch::TensorOptions().dtype(torch::kInt32).device(vks.device()));
+    auto ok = torch::zeros({N}, opts(torch::kInt32, vks));
     if (N > 0) {
         launch_k1_bls_verify2(vks.data_ptr<uint8_t>(), sigs.data_ptr<uint8_t>(),
                               msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(),
@@ -291,7 +230,7 @@ torch::Tensor bls_verify_batch_wave(torch::Tensor vks, torch::Tensor sigs,
     int32_t N = (int32_t)moff.size(0) - 1;
     TORCH_CHECK(vks.numel() == (int64_t)N * 128 && sigs.numel() == (int64_t)N * 64);
     TORCH_CHECK(rand_r.numel() >= N && rand_r.dtype() == torch::kInt64);
-    auto ok = torch::zeros({N}, torch::TensorOptions().dtype(torch::kInt32).device(vks.device()));
+    auto ok = torch::zeros({N}, opts(torch::kInt32, vks));
     if (N > 0) {
         launch_k1_bls_verify_wave(vks.data_ptr<uint8_t>(), sigs.data_ptr<uint8_t>(),
                                   msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(),
@@ -305,8 +244,7 @@ torch::Tensor bls_verify_batch_wave(torch::Tensor vks, torch::Tensor sigs,
 torch::Tensor hash_to_g1_batch(torch::Tensor msgs, torch::Tensor moff) {
     CHECK_DEV(msgs); CHECK_DEV(moff);
     int32_t N = (int32_t)moff.size(0) - 1;
-    auto out = torch::zeros({N, 64},
-                            torch::TensorOptions().dtype(torch::kUInt8).device(msgs.device()));
+    auto out = torch::zeros({N, 64}, opts(torch::kUInt8, msgs));
     if (N > 0) {
         launch_k1_hash_to_g1(msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(), N,
                              out.data_ptr<uint8_t>(), cur_stream());
@@ -383,17 +321,12 @@ torch::Tensor topic_mask_t(torch::Tensor sub_bitmap, torch::Tensor buf,
                            torch::Tensor topics_off, torch::Tensor topics_cnt,
                            torch::Tensor disc) {
     CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap);
-    int32_t W = (int32_t)sub_bitmap.size(1);
-    int32_t M = (int32_t)disc.size(0);
-    auto mask_t = torch::empty({(int64_t)W, M},
-                               torch::TensorOptions().dtype(torch::kInt64).device(buf.device()));
-    if (M > 0) {
+    return k2a_mask(sub_bitmap, buf, disc, true, [&](uint64_t* mask_t, int32_t M, int32_t W) {
         launch_k2a_topic_mask_t((const uint64_t*)sub_bitmap.data_ptr<int64_t>(),
                                 buf.data_ptr<uint8_t>(), topics_off.data_ptr<int64_t>(),
                                 topics_cnt.data_ptr<int32_t>(), disc.data_ptr<int32_t>(),
-                                (uint64_t*)mask_t.data_ptr<int64_t>(), M, W, cur_stream());
-    }
-    return mask_t;
+                                mask_t, M, W, cur_stream());
+    });
 }
 
 void assign_emit_fused_t(torch::Tensor mask_t, torch::Tensor payload_len,
@@ -456,21 +389,16 @@ torch::Tensor topic_mask_origin_t(torch::Tensor sub_bitmap, torch::Tensor buf,
                                   torch::Tensor topics_off, torch::Tensor topics_cnt,
                                   torch::Tensor disc, torch::Tensor origin, int64_t n_users) {
     CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap); CHECK_DEV(origin); CHECK_CONTIG(origin);
-    int32_t W = (int32_t)sub_bitmap.size(1);
-    int32_t M = (int32_t)disc.size(0);
-    TORCH_CHECK(origin.dtype() == torch::kInt32 && origin.numel() == M,
+    TORCH_CHECK(origin.dtype() == torch::kInt32 && origin.numel() == disc.size(0),
                 "origin must be an int32 [M] tensor");
-    TORCH_CHECK(n_users >= 0 && n_users <= (int64_t)W * 64, "n_users outside the bitmap");
-    auto mask_t = torch::empty({(int64_t)W, M},
-                               torch::TensorOptions().dtype(torch::kInt64).device(buf.device()));
-    if (M > 0) {
+    TORCH_CHECK(n_users >= 0 && n_users <= sub_bitmap.size(1) * 64, "n_users outside the bitmap");
+    return k2a_mask(sub_bitmap, buf, disc, true, [&](uint64_t* mask_t, int32_t M, int32_t W) {
         launch_k2a_topic_mask_origin_t(
             (const uint64_t*)sub_bitmap.data_ptr<int64_t>(), buf.data_ptr<uint8_t>(),
             topics_off.data_ptr<int64_t>(), topics_cnt.data_ptr<int32_t>(),
-            disc.data_ptr<int32_t>(), origin.data_ptr<int32_t>(),
-            (uint64_t*)mask_t.data_ptr<int64_t>(), M, W, (int32_t)n_users, cur_stream());
-    }
-    return mask_t;
+            disc.data_ptr<int32_t>(), origin.data_ptr<int32_t>(), mask_t, M, W,
+            (int32_t)n_users, cur_stream());
+    });
 }
 
 void emit_direct_peers(torch::Tensor disc, torch::Tensor owner, torch::Tensor origin,
@@ -542,8 +470,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           [](torch::Tensor vks, torch::Tensor sigs, torch::Tensor msgs, torch::Tensor moff,
              torch::Tensor g2_lines, torch::Tensor rand_r, int64_t mode) {
               int32_t N = (int32_t)moff.size(0) - 1;
-              auto ok = torch::zeros({N}, torch::TensorOptions().dtype(torch::kInt32)
-                                              .device(vks.device()));
+              auto ok = torch::zeros({N}, opts(torch::kInt32, vks));
               launch_k1_dbg_wave(vks.data_ptr<uint8_t>(), sigs.data_ptr<uint8_t>(),
                                  msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(),
                                  g2_lines.data_ptr<uint8_t>(),

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../bls/bls.h"
+#include "bls_kernels.h"
 #include "bn254_pair2.h"
 
 using namespace bn254;

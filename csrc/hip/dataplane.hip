@@ -45,6 +45,21 @@
 //                        per-message origin (single-hop broker plane)
 //   K6  k6_direct_apply — batched DirectMap upserts/deletes (CAS insert,
 //                        tombstoned values)
+//   K7  k7_compact_rings — gather used ring prefixes into one staging buffer
+//
+// Shared device building blocks, each defined once and force-inlined:
+//   store16<NT>        the only place the non-temporal store choice is made
+//   store_pair         one dword4 store of a PairRec
+//   copy_record<NT>    record header + aligned/unaligned 16 B loop + byte
+//                      tail over (lane, lane count) — k3_fanout, _wave_t, _ref_t
+//   topic_row_or       OR of a message's topic rows for one mask word — the
+//                      three K2a kernels
+//   wave_claim_span    wave64 inclusive scan + one atomicAdd per wave —
+//                      k2b_fused_t, k2b_p2_bases
+//   k5b_claim_emit     pair-slot claim, CAS ring claim, placeholder and drop
+//                      — both K5b kernels
+// The launcher prototypes and the PairRec / ParseOut structs are in
+// dataplane.h, shared with the host-only bindings.
 //
 // Design notes (per /opt/skills/guides/cdna_hip_programming.md):
 //  - wave = 64; all copies are uint4 (16 B/lane) vectorized
@@ -60,6 +75,7 @@
 #include <stdint.h>
 
 #include "../common/divmagic.h"
+#include "dataplane.h"
 
 #define WAVE 64
 #ifndef CDN_CHECK
@@ -78,17 +94,21 @@ __host__ __device__ inline uint64_t ring_rec(int32_t len) {
     return ((uint64_t)len + 16 + (RING_ALIGN - 1)) & ~(RING_ALIGN - 1);
 }
 
-// A delivery pair as ONE 16-byte record {user, msg, ring dst}: emitters do a
-// single dword4 store per pair and K3 a single dword4 load per unit.  The
-// SoA layout (three arrays) cost ~3x scattered sub-line stores per pair —
-// measured 100 us/tick in k2b_p3_emit at 2.56M pairs before this change.
-struct alignas(16) PairRec { int32_t user; int32_t msg; int64_t dst; };
-static_assert(sizeof(PairRec) == 16, "PairRec must be one dword4");
+// One 16-byte (dword4) store to a 16-aligned address.  NT=1 is non-temporal:
+// egress bytes are written once and consumed by the D2H drain, so they should
+// not evict the hot message source bytes from the per-XCD L2.
 typedef unsigned int cdn_v4u __attribute__((ext_vector_type(4)));
-__device__ inline void store_pair(PairRec* p, int32_t u, int32_t m, int64_t d) {
+template <int NT>
+__device__ __forceinline__ void store16(void* dst, cdn_v4u v) {
+    if (NT) __builtin_nontemporal_store(v, (cdn_v4u*)dst);
+    else *(cdn_v4u*)dst = v;
+}
+
+// A delivery pair (PairRec, dataplane.h) is stored as ONE dword4.
+__device__ __forceinline__ void store_pair(PairRec* p, int32_t u, int32_t m, int64_t d) {
     PairRec r{u, m, d};
     cdn_v4u v; memcpy(&v, &r, 16);
-    *(cdn_v4u*)p = v;
+    store16<0>(p, v);
 }
 
 // ---------------------------------------------------------------------------
@@ -120,17 +140,8 @@ __host__ __device__ inline uint64_t fnv1a64(const uint8_t* data, uint32_t len,
 //   topics_off/cnt  topic list byte range (Broadcast/Subscribe/Unsubscribe)
 //   recip_hash      fnv1a64 of the recipient key (Direct), else 0
 //   timestamp       AuthenticateWithKey.timestamp, else 0
+// (struct ParseOut, dataplane.h)
 // ---------------------------------------------------------------------------
-
-struct ParseOut {
-    int32_t* disc;
-    int64_t* payload_off;
-    int32_t* payload_len;
-    int64_t* topics_off;
-    int32_t* topics_cnt;
-    uint64_t* recip_hash;
-    uint64_t* timestamp;
-};
 
 __device__ inline uint64_t ld_u64(const uint8_t* p) {
     uint64_t v;
@@ -300,6 +311,40 @@ extern "C" __global__ void k4_parse_batch(
 // (reference tests: no echo to the originating connection is NOT default —
 // the reference DOES echo to the sender if subscribed; keep -1 to disable).
 // ---------------------------------------------------------------------------
+
+// Bits of mask word w that belong to local users (recipients < n_users).
+__device__ __forceinline__ uint64_t user_bits_of_word(int32_t w, int32_t n_users) {
+    const int64_t lo = (int64_t)w * 64;
+    if ((int64_t)n_users >= lo + 64) return ~0ull;
+    if ((int64_t)n_users <= lo) return 0ull;
+    return (1ull << (n_users - lo)) - 1ull;
+}
+
+// Word w of message m's recipient mask: the OR of its topic rows, or 0 for
+// anything but a Broadcast.  Shared by the three K2a kernels, which differ
+// only in where they store the word and in the origin filter: with
+// SINGLE_HOP, a message that arrived from a peer broker (origin[m] != 0)
+// keeps only its local-user bits (see "Peer-broker recipients").  m is taken
+// as int64_t so that the caller's one widening of the message index serves
+// the loads here and its own store index (with int m the origin kernel came
+// out two VGPRs larger).
+template <bool SINGLE_HOP>
+__device__ __forceinline__ uint64_t topic_row_or(
+    const uint64_t* __restrict__ sub_bitmap, const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ topics_off, const int32_t* __restrict__ topics_cnt,
+    const int32_t* __restrict__ disc, int64_t m, int w, int32_t W,
+    const int32_t* __restrict__ origin, int32_t n_users)
+{
+    uint64_t acc = 0;
+    if (disc[m] == 4) {
+        const uint8_t* topics = buf + topics_off[m];
+        int n = topics_cnt[m];
+        for (int t = 0; t < n; ++t) acc |= sub_bitmap[(int64_t)topics[t] * W + w];
+        if (SINGLE_HOP && origin[m] != 0) acc &= user_bits_of_word(w, n_users);
+    }
+    return acc;
+}
+
 extern "C" __global__ void k2a_topic_mask(
     const uint64_t* __restrict__ sub_bitmap,  // [256][W]
     const uint8_t* __restrict__ buf,
@@ -313,15 +358,8 @@ extern "C" __global__ void k2a_topic_mask(
     if (idx >= (int64_t)M * W) return;
     int m = idx / W;
     int w = idx % W;
-    uint64_t acc = 0;
-    if (disc[m] == 4) {
-        const uint8_t* topics = buf + topics_off[m];
-        int n = topics_cnt[m];
-        for (int t = 0; t < n; ++t) {
-            acc |= sub_bitmap[(int64_t)topics[t] * W + w];
-        }
-    }
-    mask[idx] = acc;
+    mask[idx] = topic_row_or<false>(sub_bitmap, buf, topics_off, topics_cnt, disc, m, w, W,
+                                    nullptr, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -333,8 +371,9 @@ extern "C" __global__ void k2a_topic_mask(
 // grouped by user and ordered by message within each user.
 //
 // egress ring layout: ring_bytes per user within a single [N_users][ring_bytes]
-// tensor. Each delivery writes an 8-byte record header {u32 len, u32 msg_seq}
-// followed by the payload, 8-byte aligned (the host-side drain parses this).
+// tensor. Each delivery writes a 16-byte record header {u32 len, u32 msg_seq,
+// 0, 0} followed by the payload, padded to a 16-byte stride (ring_rec; the
+// host-side drain parses this).
 // If the ring fills, the remaining deliveries for that user are dropped and
 // counted (best-effort semantics = reference eviction-on-full, sender.rs).
 // ---------------------------------------------------------------------------
@@ -373,7 +412,7 @@ extern "C" __global__ void k2b_emit(
     for (int m = 0; m < M; ++m) {
         if (!(mask[(int64_t)m * W + w] & bit)) continue;
         int32_t len = payload_len[m];
-        // 64-aligned record stride (see ring_rec)
+        // 16-aligned record stride (see ring_rec)
         uint64_t rec = ring_rec(len);
         if (wpos + rec > (uint64_t)ring_bytes) {
             store_pair(pairs + slot, -1, m, 0);
@@ -390,9 +429,39 @@ extern "C" __global__ void k2b_emit(
 // ---------------------------------------------------------------------------
 // K3: fan-out payload copy. Grid-stride over delivery pairs; each workgroup
 // copies one pair per iteration with 16 B/lane vector loads/stores. Writes
-// the 8-byte record header, then the payload. Source bytes for a hot message
+// the 16-byte record header, then the payload. Source bytes for a hot message
 // are L2/LLC-resident after the first few recipients.
 // ---------------------------------------------------------------------------
+
+// Cooperative copy of one inline record by `nlanes` lanes, this one being
+// `lane`: lane 0 stores the header {len, seq, 0, 0}, then all lanes copy the
+// payload in 16 B chunks and the last len % 16 bytes one by one.  dst is a
+// record start, so it is 16-aligned (ring base and ring_rec stride are); a
+// source that is not takes the byte-wise chunk loop, which stores plainly at
+// either NT.  The one definition of an inline record's bytes: k3_fanout
+// (a workgroup per record), k3_fanout_wave_t and k3_fanout_ref_t (a wave per
+// record) all call it.
+template <int NT>
+__device__ __forceinline__ void copy_record(uint8_t* dst, const uint8_t* src, int32_t len,
+                                            uint32_t seq, int lane, int nlanes)
+{
+    if (lane == 0) store16<NT>(dst, cdn_v4u{(uint32_t)len, seq, 0u, 0u});
+    dst += 16;
+    const int32_t nvec = len >> 4;  // full 16-byte chunks
+    if ((((uintptr_t)src) & 15) == 0) {
+        const cdn_v4u* s4 = (const cdn_v4u*)src;
+        cdn_v4u* d4 = (cdn_v4u*)dst;
+        for (int k = lane; k < nvec; k += nlanes) store16<NT>(d4 + k, s4[k]);
+    } else {
+        for (int k = lane; k < nvec; k += nlanes) {
+            uint8_t tmp[16];
+            memcpy(tmp, src + (size_t)k * 16, 16);
+            memcpy(dst + (size_t)k * 16, tmp, 16);
+        }
+    }
+    for (int k = (nvec << 4) + lane; k < len; k += nlanes) dst[k] = src[k];
+}
+
 extern "C" __global__ void k3_fanout(
     const uint8_t* __restrict__ buf,
     const int64_t* __restrict__ payload_off,
@@ -406,29 +475,8 @@ extern "C" __global__ void k3_fanout(
         const PairRec pr = pairs[p];
         if (pr.user < 0) continue;  // dropped (ring full)
         int m = pr.msg;
-        int32_t len = payload_len[m];
-        const uint8_t* src = buf + payload_off[m];
-        uint8_t* dst = egress + pr.dst;
-        if (threadIdx.x == 0) {
-            uint32_t hdr[4] = {(uint32_t)len, msg_seq[m], 0, 0};
-            memcpy(dst, hdr, 16);
-        }
-        dst += 16;  // 16-aligned: ring base and every record start are 16-aligned
-        int32_t nvec = len >> 4;          // full 16-byte chunks
-        const bool src16 = (((uintptr_t)src) & 15) == 0;
-        if (src16) {
-            const uint4* s4 = (const uint4*)src;
-            uint4* d4 = (uint4*)dst;
-            for (int k = threadIdx.x; k < nvec; k += blockDim.x) d4[k] = s4[k];
-        } else {
-            for (int k = threadIdx.x; k < nvec; k += blockDim.x) {
-                uint8_t tmp[16];
-                memcpy(tmp, src + (size_t)k * 16, 16);
-                memcpy(dst + (size_t)k * 16, tmp, 16);
-            }
-        }
-        for (int k = (nvec << 4) + threadIdx.x; k < len; k += blockDim.x)
-            dst[k] = src[k];
+        copy_record<0>(egress + pr.dst, buf + payload_off[m], payload_len[m], msg_seq[m],
+                       threadIdx.x, blockDim.x);
     }
 }
 
@@ -488,7 +536,7 @@ extern "C" __global__ void k2c_apply_subs(
         const uint8_t* topics = buf + topics_off[m];
         int n = topics_cnt[m];
         for (int t = 0; t < n; ++t) {
-            uint64_t* word = &sub_bitmap[(int64_t)topics[t] * W + w];
+            uint64_t* word = sub_bitmap + ((int64_t)topics[t] * W + w);
             if (d == 5) *word |= bit;
             else        *word &= ~bit;
         }
@@ -499,6 +547,22 @@ extern "C" __global__ void k2c_apply_subs(
 // Host-side launchers (called from the torch-extension bindings, which are
 // compiled as plain host C++ and cannot reference __global__ symbols).
 // ---------------------------------------------------------------------------
+
+// Runs `launch` with NT bound to the compile-time constant 1 or 0 according
+// to the launcher's run-time `nt` flag (the kernels take NT as a template
+// parameter).
+#define DISPATCH_NT(nt, launch)                   \
+    do {                                          \
+        if (nt) { constexpr int NT = 1; launch; } \
+        else    { constexpr int NT = 0; launch; } \
+    } while (0)
+
+// K2a grid: one thread per (message, mask word).
+#define K2A_THREADS 256
+static inline dim3 k2a_grid(int32_t M, int32_t W) {
+    return dim3((uint32_t)(((int64_t)M * W + K2A_THREADS - 1) / K2A_THREADS));
+}
+
 extern "C" {
 
 void launch_k4_parse(const uint8_t* buf, const int64_t* offsets, int32_t M, uint64_t hash_seed,
@@ -514,11 +578,8 @@ void launch_k2a_topic_mask(const uint64_t* sub_bitmap, const uint8_t* buf,
                            const int32_t* disc, uint64_t* mask, int32_t M, int32_t W,
                            hipStream_t s) {
     if (M <= 0) return;
-    int64_t total = (int64_t)M * W;
-    int threads = 256;
-    int64_t blocks = (total + threads - 1) / threads;
-    hipLaunchKernelGGL(k2a_topic_mask, dim3((uint32_t)blocks), dim3(threads), 0, s, sub_bitmap,
-                       buf, topics_off, topics_cnt, disc, mask, M, W);
+    hipLaunchKernelGGL(k2a_topic_mask, k2a_grid(M, W), dim3(K2A_THREADS), 0, s, sub_bitmap, buf,
+                       topics_off, topics_cnt, disc, mask, M, W);
 }
 
 void launch_k2b_count(const uint64_t* mask, int32_t M, int32_t W, int32_t n_users,
@@ -598,38 +659,7 @@ __global__ void __launch_bounds__(256) k3_fanout_wave_t(
         if (pr.user < 0) continue;
         const int mi = pr.msg;
         const int32_t len = payload_len[mi];
-        const uint8_t* src = buf + payload_off[mi];
-        uint8_t* dst = egress + pr.dst;
-        if (lane == 0) {
-            uint32_t hdr[4] = {(uint32_t)len, msg_seq[mi], 0, 0};
-            if (NT) {
-                typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-                v4u h; memcpy(&h, hdr, 16);
-                __builtin_nontemporal_store(h, (v4u*)dst);
-            } else {
-                memcpy(dst, hdr, 16);
-            }
-        }
-        dst += 16;
-        const int32_t nvec = len >> 4;
-        const bool src16 = (((uintptr_t)src) & 15) == 0;
-        if (src16) {
-            typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-            const v4u* s4 = (const v4u*)src;
-            v4u* d4 = (v4u*)dst;
-            for (int k = lane; k < nvec; k += 64) {
-                v4u v = s4[k];
-                if (NT) __builtin_nontemporal_store(v, d4 + k);
-                else d4[k] = v;
-            }
-        } else {
-            for (int k = lane; k < nvec; k += 64) {
-                uint8_t tmp[16];
-                memcpy(tmp, src + (size_t)k * 16, 16);
-                memcpy(dst + (size_t)k * 16, tmp, 16);
-            }
-        }
-        for (int k = (nvec << 4) + lane; k < len; k += 64) dst[k] = src[k];
+        copy_record<NT>(egress + pr.dst, buf + payload_off[mi], len, msg_seq[mi], lane, WAVE);
     }
 }
 
@@ -641,16 +671,10 @@ void launch_k3_fanout_wave(const uint8_t* buf, const int64_t* payload_off,
                            int32_t capacity,
                            uint8_t* egress, int nt, int grid, hipStream_t s) {
     if (grid <= 0) grid = 4096;  // 4096 WGs x 4 waves = 16384 concurrent pairs
-    if (nt)
-        hipLaunchKernelGGL((k3_fanout_wave_t<1>), dim3(grid), dim3(256), 0, s, buf, payload_off,
-                           payload_len, pairs, msg_seq, n_pairs_ptr, capacity,
-                           egress);
-    else
-        hipLaunchKernelGGL((k3_fanout_wave_t<0>), dim3(grid), dim3(256), 0, s, buf, payload_off,
-                           payload_len, pairs, msg_seq, n_pairs_ptr, capacity,
-                           egress);
+    DISPATCH_NT(nt, hipLaunchKernelGGL((k3_fanout_wave_t<NT>), dim3(grid), dim3(256), 0, s, buf,
+                                       payload_off, payload_len, pairs, msg_seq, n_pairs_ptr,
+                                       capacity, egress));
 }
-
 
 }  // extern "C"
 
@@ -659,16 +683,15 @@ void launch_k3_fanout_wave(const uint8_t* buf, const int64_t* payload_off,
 // kernel; a message of at least ref_threshold bytes is delivered as a bare
 // 16 B header {u32 len | REF_FLAG, u32 seq, u64 ref_base + payload_off[msg]}
 // and its payload stays in the host's copy of the batch; any shorter message
-// is written exactly as k3_fanout_wave_t writes it.
+// is written by copy_record, the same call k3_fanout_wave_t makes.
 //
 // Work split: a wave owns G CONSECUTIVE pairs per grid-stride step, one
 // pair per lane (lanes >= G hold none).  The by-reference lanes store their
 // header together (one dword4 store per lane, one wave instruction for up to
 // G pairs) — a wave per pair would spend a whole wave on each 16 B store.
 // The wave then walks the ballot of inline lanes, broadcasts that lane's
-// pair through __shfl and copies the record cooperatively (64 lanes x 16 B
-// per pass), with the wave kernel's aligned / unaligned source branches,
-// byte tail and NT option.
+// pair through __shfl and copies the record cooperatively with copy_record
+// (64 lanes x 16 B per pass).
 //
 // G is the smallest power of two, at most 64, at which one step of all the
 // grid's waves covers the pair list.  A fixed G = 64 was measured first: it
@@ -721,9 +744,8 @@ __global__ void __launch_bounds__(256) k3_fanout_ref_t(
         const bool by_ref = live && len >= ref_threshold;
         if (by_ref) {
             const uint64_t ro = (uint64_t)(ref_base + off);
-            cdn_v4u h = {(uint32_t)len | REF_FLAG, seq, (uint32_t)ro, (uint32_t)(ro >> 32)};
-            if (NT) __builtin_nontemporal_store(h, (cdn_v4u*)(egress + dsto));
-            else *(cdn_v4u*)(egress + dsto) = h;
+            store16<NT>(egress + dsto, cdn_v4u{(uint32_t)len | REF_FLAG, seq, (uint32_t)ro,
+                                               (uint32_t)(ro >> 32)});
         }
         // every lane of the wave reaches the ballot and the shuffles below
         unsigned long long inl = __ballot(live && !by_ref);
@@ -736,31 +758,7 @@ __global__ void __launch_bounds__(256) k3_fanout_ref_t(
                                  | (uint32_t)__shfl((int)off, j);
             const int64_t jdst = ((int64_t)__shfl((int)(dsto >> 32), j) << 32)
                                  | (uint32_t)__shfl((int)dsto, j);
-            const uint8_t* src = buf + joff;
-            uint8_t* dst = egress + jdst;
-            if (lane == 0) {
-                cdn_v4u h = {(uint32_t)jlen, jseq, 0u, 0u};
-                if (NT) __builtin_nontemporal_store(h, (cdn_v4u*)dst);
-                else *(cdn_v4u*)dst = h;
-            }
-            dst += 16;
-            const int32_t nvec = jlen >> 4;
-            if ((((uintptr_t)src) & 15) == 0) {
-                const cdn_v4u* s4 = (const cdn_v4u*)src;
-                cdn_v4u* d4 = (cdn_v4u*)dst;
-                for (int k = lane; k < nvec; k += 64) {
-                    cdn_v4u v = s4[k];
-                    if (NT) __builtin_nontemporal_store(v, d4 + k);
-                    else d4[k] = v;
-                }
-            } else {
-                for (int k = lane; k < nvec; k += 64) {
-                    uint8_t tmp[16];
-                    memcpy(tmp, src + (size_t)k * 16, 16);
-                    memcpy(dst + (size_t)k * 16, tmp, 16);
-                }
-            }
-            for (int k = (nvec << 4) + lane; k < jlen; k += 64) dst[k] = src[k];
+            copy_record<NT>(egress + jdst, buf + joff, jlen, jseq, lane, WAVE);
         }
     }
 }
@@ -773,14 +771,9 @@ void launch_k3_fanout_ref(const uint8_t* buf, const int64_t* payload_off,
                           int32_t capacity, int32_t ref_threshold, int64_t ref_base,
                           uint8_t* egress, int nt, int grid, hipStream_t s) {
     if (grid <= 0) grid = 4096;  // 4096 WGs x 4 waves, up to 64 pairs per wave and step
-    if (nt)
-        hipLaunchKernelGGL((k3_fanout_ref_t<1>), dim3(grid), dim3(256), 0, s, buf, payload_off,
-                           payload_len, pairs, msg_seq, n_pairs_ptr, capacity,
-                           ref_threshold, ref_base, egress);
-    else
-        hipLaunchKernelGGL((k3_fanout_ref_t<0>), dim3(grid), dim3(256), 0, s, buf, payload_off,
-                           payload_len, pairs, msg_seq, n_pairs_ptr, capacity,
-                           ref_threshold, ref_base, egress);
+    DISPATCH_NT(nt, hipLaunchKernelGGL((k3_fanout_ref_t<NT>), dim3(grid), dim3(256), 0, s, buf,
+                                       payload_off, payload_len, pairs, msg_seq, n_pairs_ptr,
+                                       capacity, ref_threshold, ref_base, egress));
 }
 
 }  // extern "C"
@@ -814,7 +807,6 @@ __global__ void __launch_bounds__(256) k3_fanout_flat_t(
                                           // skips the per-unit length load
     uint8_t* __restrict__ egress)
 {
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
     const uint32_t seq_base = SEQ_FROM_PTR ? seq_state[0] : seq_base_val;
     int np = *n_pairs_ptr;
     if (np > capacity) np = capacity;
@@ -830,32 +822,24 @@ __global__ void __launch_bounds__(256) k3_fanout_flat_t(
         const int32_t len = uniform_len > 0 ? uniform_len : payload_len[mi];
         uint8_t* dst = egress + pr.dst + (size_t)unit * 16;
         if (unit == 0) {
-            uint32_t hdr[4] = {(uint32_t)len, seq_base + (uint32_t)mi, 0, 0};
-            v4u h; memcpy(&h, hdr, 16);
-            if (NT) __builtin_nontemporal_store(h, (v4u*)dst);
-            else memcpy(dst, hdr, 16);
+            store16<NT>(dst, cdn_v4u{(uint32_t)len, seq_base + (uint32_t)mi, 0u, 0u});
             continue;
         }
         const uint8_t* src = buf + payload_off[mi] + (size_t)(unit - 1) * 16;
         const int32_t coff = (unit - 1) * 16;
         if (coff + 16 <= len && (((uintptr_t)src) & 15) == 0) {
-            v4u v = *(const v4u*)src;
-            if (NT) __builtin_nontemporal_store(v, (v4u*)dst);
-            else *(v4u*)dst = v;
+            store16<NT>(dst, *(const cdn_v4u*)src);
         } else if (coff >= len) {
             // pure pad unit: zero store so the record stride is fully
             // written (full-line NT writes, no RMW at record boundaries)
-            v4u z = {0, 0, 0, 0};
-            if (NT) __builtin_nontemporal_store(z, (v4u*)dst);
-            else *(v4u*)dst = z;
+            store16<NT>(dst, cdn_v4u{0u, 0u, 0u, 0u});
         } else {
             // partial tail unit: zero-fill to one full 16 B store
             uint8_t tmp[16];
             #pragma unroll
             for (int b = 0; b < 16; ++b) tmp[b] = (coff + b < len) ? src[b] : 0;
-            v4u v; memcpy(&v, tmp, 16);
-            if (NT) __builtin_nontemporal_store(v, (v4u*)dst);
-            else *(v4u*)dst = v;
+            cdn_v4u v; memcpy(&v, tmp, 16);
+            store16<NT>(dst, v);
         }
     }
 }
@@ -864,45 +848,19 @@ __global__ void __launch_bounds__(256) k3_fanout_flat_t(
 // f < 2^31 and 1 <= d <= 2^21 — the bindings enforce both bounds
 // (units_per_pair <= 2^21, capacity * units_per_pair < 2^31) before launch.
 
-extern "C" void launch_k3_fanout_flat2(
-    const uint8_t* buf, const int64_t* payload_off, const int32_t* payload_len,
-    const PairRec* pairs,
-    uint32_t seq_base, const int32_t* n_pairs_ptr, int32_t capacity, int32_t units_per_pair, int32_t uniform_len,
-    uint8_t* egress, int nt, int grid, hipStream_t s) {
+template <bool SEQ_FROM_PTR>
+static void launch_flat(const uint8_t* buf, const int64_t* payload_off,
+                        const int32_t* payload_len, const PairRec* pairs, uint32_t seq_base,
+                        const uint32_t* seq_state, const int32_t* n_pairs_ptr, int32_t capacity,
+                        int32_t units_per_pair, int32_t uniform_len, uint8_t* egress, int nt,
+                        int grid, hipStream_t s) {
     if (grid <= 0) grid = 16384;  // swept: 16384 > 8192 > 4096 (~0.5% each)
     uint32_t dm; int32_t dsh;
     u32_div_magic(units_per_pair, &dm, &dsh);
-    if (nt)
-        hipLaunchKernelGGL((k3_fanout_flat_t<1, false>), dim3(grid), dim3(256), 0, s, buf,
-                           payload_off, payload_len, pairs, seq_base,
-                           nullptr, n_pairs_ptr, capacity, units_per_pair, dm, dsh,
-                           uniform_len, egress);
-    else
-        hipLaunchKernelGGL((k3_fanout_flat_t<0, false>), dim3(grid), dim3(256), 0, s, buf,
-                           payload_off, payload_len, pairs, seq_base,
-                           nullptr, n_pairs_ptr, capacity, units_per_pair, dm, dsh,
-                           uniform_len, egress);
-}
-
-extern "C" void launch_k3_fanout_flat3(
-    const uint8_t* buf, const int64_t* payload_off, const int32_t* payload_len,
-    const PairRec* pairs,
-    const uint32_t* seq_state, const int32_t* n_pairs_ptr, int32_t capacity,
-    int32_t units_per_pair, int32_t uniform_len, uint8_t* egress, int nt, int grid,
-    hipStream_t s) {
-    if (grid <= 0) grid = 16384;
-    uint32_t dm; int32_t dsh;
-    u32_div_magic(units_per_pair, &dm, &dsh);
-    if (nt)
-        hipLaunchKernelGGL((k3_fanout_flat_t<1, true>), dim3(grid), dim3(256), 0, s, buf,
-                           payload_off, payload_len, pairs, 0u,
-                           seq_state, n_pairs_ptr, capacity, units_per_pair, dm, dsh,
-                           uniform_len, egress);
-    else
-        hipLaunchKernelGGL((k3_fanout_flat_t<0, true>), dim3(grid), dim3(256), 0, s, buf,
-                           payload_off, payload_len, pairs, 0u,
-                           seq_state, n_pairs_ptr, capacity, units_per_pair, dm, dsh,
-                           uniform_len, egress);
+    DISPATCH_NT(nt, hipLaunchKernelGGL((k3_fanout_flat_t<NT, SEQ_FROM_PTR>), dim3(grid),
+                                       dim3(256), 0, s, buf, payload_off, payload_len, pairs,
+                                       seq_base, seq_state, n_pairs_ptr, capacity,
+                                       units_per_pair, dm, dsh, uniform_len, egress));
 }
 
 extern "C" __global__ void k_seq_advance(uint32_t* seq_state, int32_t m) {
@@ -911,6 +869,23 @@ extern "C" __global__ void k_seq_advance(uint32_t* seq_state, int32_t m) {
 
 extern "C" {
 
+void launch_k3_fanout_flat2(const uint8_t* buf, const int64_t* payload_off,
+                            const int32_t* payload_len, const PairRec* pairs,
+                            uint32_t seq_base, const int32_t* n_pairs_ptr, int32_t capacity,
+                            int32_t units_per_pair, int32_t uniform_len, uint8_t* egress,
+                            int nt, int grid, hipStream_t s) {
+    launch_flat<false>(buf, payload_off, payload_len, pairs, seq_base, nullptr, n_pairs_ptr,
+                       capacity, units_per_pair, uniform_len, egress, nt, grid, s);
+}
+
+void launch_k3_fanout_flat3(const uint8_t* buf, const int64_t* payload_off,
+                            const int32_t* payload_len, const PairRec* pairs,
+                            const uint32_t* seq_state, const int32_t* n_pairs_ptr,
+                            int32_t capacity, int32_t units_per_pair, int32_t uniform_len,
+                            uint8_t* egress, int nt, int grid, hipStream_t s) {
+    launch_flat<true>(buf, payload_off, payload_len, pairs, 0u, seq_state, n_pairs_ptr,
+                      capacity, units_per_pair, uniform_len, egress, nt, grid, s);
+}
 
 void launch_k_seq_advance(uint32_t* seq_state, int32_t m, hipStream_t s) {
     hipLaunchKernelGGL(k_seq_advance, dim3(1), dim3(1), 0, s, seq_state, m);
@@ -936,21 +911,35 @@ extern "C" __global__ void k2a_topic_mask_t(
     if (idx >= (int64_t)M * W) return;
     int m = idx / W;
     int w = idx % W;
-    uint64_t acc = 0;
-    if (disc[m] == 4) {
-        const uint8_t* topics = buf + topics_off[m];
-        int n = topics_cnt[m];
-        for (int t = 0; t < n; ++t) acc |= sub_bitmap[(int64_t)topics[t] * W + w];
+    mask_t[(int64_t)w * M + m] =
+        topic_row_or<false>(sub_bitmap, buf, topics_off, topics_cnt, disc, m, w, W, nullptr, 0);
+}
+
+// Wave-aggregated span claim: a wave64 inclusive scan of the lanes' counts
+// and ONE atomicAdd of the wave's total on `counter` (157 atomics for 10k
+// users instead of 10k — a single counter word saturates at ~88 atomics/us,
+// MI355X_MICROARCH 'dequeue' row).  Returns the first slot of this lane's
+// `count` consecutive slots; the wave's spans are contiguous in lane order.
+// EVERY lane of the wave must reach this call (it shuffles): a caller whose
+// lane has no work passes count = 0 and returns only afterwards.
+__device__ __forceinline__ int wave_claim_span(int count, int32_t* __restrict__ counter) {
+    const int lane = threadIdx.x & 63;
+    int incl = count;
+    for (int d = 1; d < 64; d <<= 1) {
+        int ngh = __shfl_up(incl, d);
+        if (lane >= d) incl += ngh;
     }
-    mask_t[(int64_t)w * M + m] = acc;
+    int wave_total = __shfl(incl, 63);
+    int base = 0;
+    if (lane == 0 && wave_total > 0) base = atomicAdd(counter, wave_total);
+    base = __shfl(base, 0);
+    return base + incl - count;
 }
 
 // uniform_rec != 0: every record in this tick is uniform_rec bytes (the
 // uniform-wire broadcast shape) — ring math is closed-form and payload_len
-// is never loaded. Slot claims are WAVE-AGGREGATED: a wave64 prefix-scan of
-// per-lane counts and ONE atomicAdd per wave (157 atomics for 10k users
-// instead of 10k — a single counter word saturates at ~88 atomics/us,
-// MI355X_MICROARCH 'dequeue' row) keep the pair list contiguous.
+// is never loaded. Slot claims are wave-aggregated (wave_claim_span), which
+// keeps the pair list contiguous.
 extern "C" __global__ void k2b_fused_t(
     const uint64_t* __restrict__ mask_t,      // [W][M]
     const int32_t* __restrict__ payload_len,
@@ -971,18 +960,8 @@ extern "C" __global__ void k2b_fused_t(
 #pragma unroll 8
         for (int m = 0; m < M; ++m) count += (col[m] & bit) ? 1 : 0;
     }
-    // wave64 inclusive scan of counts; one atomic per wave claims the span
-    const int lane = threadIdx.x & 63;
-    int incl = count;
-    for (int d = 1; d < 64; d <<= 1) {
-        int ngh = __shfl_up(incl, d);
-        if (lane >= d) incl += ngh;
-    }
-    int wave_total = __shfl(incl, 63);
-    int base = 0;
-    if (lane == 0 && wave_total > 0) base = atomicAdd(n_pairs, wave_total);
-    base = __shfl(base, 0);
-    int slot = base + incl - count;
+    // inactive lanes carry count = 0 through the wave-wide claim
+    int slot = wave_claim_span(count, n_pairs);
     if (!active || count == 0) return;
 
     if (uniform_rec) {
@@ -1036,11 +1015,8 @@ void launch_k2a_topic_mask_t(const uint64_t* sub_bitmap, const uint8_t* buf,
                              const int32_t* disc, uint64_t* mask_t, int32_t M, int32_t W,
                              hipStream_t s) {
     if (M <= 0) return;
-    int64_t total = (int64_t)M * W;
-    int threads = 256;
-    int64_t blocks = (total + threads - 1) / threads;
-    hipLaunchKernelGGL(k2a_topic_mask_t, dim3((uint32_t)blocks), dim3(threads), 0, s,
-                       sub_bitmap, buf, topics_off, topics_cnt, disc, mask_t, M, W);
+    hipLaunchKernelGGL(k2a_topic_mask_t, k2a_grid(M, W), dim3(K2A_THREADS), 0, s, sub_bitmap,
+                       buf, topics_off, topics_cnt, disc, mask_t, M, W);
 }
 
 // ---------------------------------------------------------------------------
@@ -1097,17 +1073,8 @@ extern "C" __global__ void k2b_p2_bases(
             total += bcount[(int64_t)b * (W * 64) + u];
         }
     }
-    // wave-aggregated claim of the contiguous per-user span
-    int incl = total;
-    for (int d = 1; d < 64; d <<= 1) {
-        int ngh = __shfl_up(incl, d);
-        if (lane >= d) incl += ngh;
-    }
-    int wave_total = __shfl(incl, 63);
-    int base = 0;
-    if (lane == 0 && wave_total > 0) base = atomicAdd(n_pairs, wave_total);
-    base = __shfl(base, 0);
-    const int my_base = base + incl - total;
+    // the contiguous per-user span; inactive lanes carry total = 0 through it
+    const int my_base = wave_claim_span(total, n_pairs);
     uint32_t dropped = 0;
     if (active) {
         ubase[u] = my_base;
@@ -1205,6 +1172,42 @@ void launch_k2b_fused_t(const uint64_t* mask_t, const int32_t* payload_len, int3
 // a delivery pair. Replaces the host-side direct routing loop (which cost a
 // D2H sync per tick).
 // ---------------------------------------------------------------------------
+
+// Claim a pair slot and `len` payload bytes of ring u for message i, then
+// store the pair.  No pair slot left: count a drop, store nothing.  Ring
+// full: store a user = -1 placeholder (K3 skips it) and count a drop.
+// Shared by both K5b kernels, which only decide u.
+__device__ __forceinline__ void k5b_claim_emit(
+    int u, int i, int32_t len, int64_t ring_bytes, int32_t capacity,
+    uint64_t* __restrict__ ring_wpos, int32_t* __restrict__ n_pairs,
+    PairRec* __restrict__ pairs, uint32_t* __restrict__ drops)
+{
+    uint64_t rec = ring_rec(len);
+    int slot = atomicAdd(n_pairs, 1);
+    if (slot >= capacity) {
+        atomicAdd(drops, 1u);
+        return;
+    }
+    // CAS claim: the round-1 add-then-rollback scheme could, with two
+    // concurrent overshooters and an interleaved accept, leave an accepted
+    // interval ABOVE a rolled-back one and let later claims overlap it.
+    // CAS never inflates the cursor, so accepted intervals are exact and
+    // a full ring drops cleanly (counted) with no spurious rollback race.
+    unsigned long long cur = atomicAdd((unsigned long long*)&ring_wpos[u], 0ull);
+    while (true) {
+        if (cur + rec > (uint64_t)ring_bytes) {
+            store_pair(pairs + slot, -1, i, 0);
+            atomicAdd(drops, 1u);
+            return;
+        }
+        unsigned long long prev = atomicCAS((unsigned long long*)&ring_wpos[u], cur,
+                                            cur + (unsigned long long)rec);
+        if (prev == cur) break;
+        cur = prev;
+    }
+    store_pair(pairs + slot, u, i, (int64_t)u * ring_bytes + (int64_t)cur);
+}
+
 extern "C" __global__ void k5b_emit_direct(
     const int32_t* __restrict__ disc,
     const int32_t* __restrict__ owner,        // K5 output; >=0 = local user
@@ -1222,31 +1225,8 @@ extern "C" __global__ void k5b_emit_direct(
     if (disc[i] != 3) return;
     int u = owner[i];
     if (u < 0) return;
-    int32_t len = payload_len[i];
-    uint64_t rec = ring_rec(len);
-    int slot = atomicAdd(n_pairs, 1);
-    if (slot >= capacity) {
-        atomicAdd(drops, 1u);
-        return;
-    }
-    // CAS claim: the round-1 add-then-rollback scheme could, with two
-    // concurrent overshooters and an interleaved accept, leave an accepted
-    // interval ABOVE a rolled-back one and let later claims overlap it.
-    // CAS never inflates the cursor, so accepted intervals are exact and
-    // a full ring drops cleanly (counted) with no spurious rollback race.
-    unsigned long long cur = atomicAdd((unsigned long long*)&ring_wpos[u], 0ull);
-    while (true) {
-        if (cur + rec > (uint64_t)ring_bytes) {
-            store_pair(pairs + slot, -1, i, 0);  // K3 skips user<0 pairs
-            atomicAdd(drops, 1u);
-            return;
-        }
-        unsigned long long prev = atomicCAS((unsigned long long*)&ring_wpos[u], cur,
-                                            cur + (unsigned long long)rec);
-        if (prev == cur) break;
-        cur = prev;
-    }
-    store_pair(pairs + slot, u, i, (int64_t)u * ring_bytes + (int64_t)cur);
+    k5b_claim_emit(u, i, payload_len[i], ring_bytes, capacity, ring_wpos, n_pairs, pairs,
+                   drops);
 }
 
 extern "C" void launch_k5b_emit_direct(
@@ -1311,16 +1291,8 @@ extern "C" void launch_k7_compact_rings(const uint8_t* egress, int64_t ring_byte
 // ring.
 // ---------------------------------------------------------------------------
 
-// Bits of mask word w that belong to local users (recipients < n_users).
-__device__ inline uint64_t user_bits_of_word(int32_t w, int32_t n_users) {
-    const int64_t lo = (int64_t)w * 64;
-    if ((int64_t)n_users >= lo + 64) return ~0ull;
-    if ((int64_t)n_users <= lo) return 0ull;
-    return (1ull << (n_users - lo)) - 1ull;
-}
-
 // K2a with origin: k2a_topic_mask_t, except that a remote-origin message
-// keeps only its local-user bits.
+// keeps only its local-user bits (topic_row_or applies user_bits_of_word).
 extern "C" __global__ void k2a_topic_mask_origin_t(
     const uint64_t* __restrict__ sub_bitmap,  // [256][W], W = ceil(R/64)
     const uint8_t* __restrict__ buf,
@@ -1335,17 +1307,12 @@ extern "C" __global__ void k2a_topic_mask_origin_t(
     if (idx >= (int64_t)M * W) return;
     int m = idx / W;
     int w = idx % W;
-    uint64_t acc = 0;
-    if (disc[m] == 4) {
-        const uint8_t* topics = buf + topics_off[m];
-        int n = topics_cnt[m];
-        for (int t = 0; t < n; ++t) acc |= sub_bitmap[(int64_t)topics[t] * W + w];
-        if (origin[m] != 0) acc &= user_bits_of_word(w, n_users);
-    }
-    mask_t[(int64_t)w * M + m] = acc;
+    mask_t[(int64_t)w * M + m] =
+        topic_row_or<true>(sub_bitmap, buf, topics_off, topics_cnt, disc, m, w, W, origin,
+                           n_users);
 }
 
-// K5b with peers: k5b_emit_direct, plus owner <= -2 -> peer slot
+// K5b with peers: k5b_emit_direct's claim, plus owner <= -2 -> peer slot
 // p = -owner-2.  A local-origin Direct to a key owned by peer p < P claims
 // space in ring n_users + p; a remote-origin one, a slot >= P and the
 // not-found value emit nothing and count no drop.  A non-negative owner
@@ -1377,27 +1344,8 @@ extern "C" __global__ void k5b_emit_direct_peers(
         if (p < 0 || p >= (int64_t)n_peers || origin[i] != 0) return;
         u = n_users + (int)p;
     }
-    int32_t len = payload_len[i];
-    uint64_t rec = ring_rec(len);
-    int slot = atomicAdd(n_pairs, 1);
-    if (slot >= capacity) {
-        atomicAdd(drops, 1u);
-        return;
-    }
-    // CAS claim, exactly as k5b_emit_direct
-    unsigned long long cur = atomicAdd((unsigned long long*)&ring_wpos[u], 0ull);
-    while (true) {
-        if (cur + rec > (uint64_t)ring_bytes) {
-            store_pair(pairs + slot, -1, i, 0);  // K3 skips user<0 pairs
-            atomicAdd(drops, 1u);
-            return;
-        }
-        unsigned long long prev = atomicCAS((unsigned long long*)&ring_wpos[u], cur,
-                                            cur + (unsigned long long)rec);
-        if (prev == cur) break;
-        cur = prev;
-    }
-    store_pair(pairs + slot, u, i, (int64_t)u * ring_bytes + (int64_t)cur);
+    k5b_claim_emit(u, i, payload_len[i], ring_bytes, capacity, ring_wpos, n_pairs, pairs,
+                   drops);
 }
 
 // ---------------------------------------------------------------------------
@@ -1474,10 +1422,7 @@ void launch_k2a_topic_mask_origin_t(const uint64_t* sub_bitmap, const uint8_t* b
                                     uint64_t* mask_t, int32_t M, int32_t W, int32_t n_users,
                                     hipStream_t s) {
     if (M <= 0) return;
-    int64_t total = (int64_t)M * W;
-    int threads = 256;
-    int64_t blocks = (total + threads - 1) / threads;
-    hipLaunchKernelGGL(k2a_topic_mask_origin_t, dim3((uint32_t)blocks), dim3(threads), 0, s,
+    hipLaunchKernelGGL(k2a_topic_mask_origin_t, k2a_grid(M, W), dim3(K2A_THREADS), 0, s,
                        sub_bitmap, buf, topics_off, topics_cnt, disc, origin, mask_t, M, W,
                        n_users);
 }

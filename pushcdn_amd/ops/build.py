@@ -39,7 +39,7 @@ def build_gpu(verbose: bool = False):
     # ninja's rules for hipcc lack header depfiles: if any shared header is
     # newer than a built object, touch the sources so the rebuild triggers.
     headers = list((CSRC / "common").glob("*.h")) + list((CSRC / "bls").glob("*.h")) \
-        + list((CSRC / "wire").glob("*.h"))
+        + list((CSRC / "wire").glob("*.h")) + list((CSRC / "hip").glob("*.h"))
     if headers:
         newest_h = max(h.stat().st_mtime for h in headers)
         for src in GPU_SOURCES:
