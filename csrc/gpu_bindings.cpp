@@ -445,7 +445,104 @@ void direct_apply(torch::Tensor table_keys, torch::Tensor table_vals, torch::Ten
                            (uint32_t*)n_failed.data_ptr<int32_t>(), cur_stream());
 }
 
+// The fused uniform broadcast tick (launch_tick_uniform_broadcast): one call
+// per tick, no allocation and no synchronisation.  scratch64 / scratch32 are
+// engine-owned and at least uniform_tick_scratch_sizes(M, W, rec) long.
+void tick_uniform_broadcast(torch::Tensor buf, torch::Tensor offsets, uint64_t hash_seed,
+                            torch::Tensor sub_bitmap, torch::Tensor ring_wpos,
+                            int64_t ring_bytes, int64_t n_users, torch::Tensor pairs,
+                            torch::Tensor drops, torch::Tensor n_pairs, torch::Tensor n_sparse,
+                            torch::Tensor scratch64, torch::Tensor scratch32,
+                            int64_t uniform_len, int64_t seq_base, torch::Tensor egress,
+                            int64_t nt, int64_t dense) {
+    CHECK_DEV(buf); CHECK_CONTIG(buf); CHECK_DEV(offsets); CHECK_CONTIG(offsets);
+    CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap); CHECK_DEV(ring_wpos); CHECK_CONTIG(ring_wpos);
+    CHECK_DEV(egress); CHECK_CONTIG(egress); CHECK_DEV(scratch64); CHECK_DEV(scratch32);
+    CHECK_DEV(drops); CHECK_DEV(n_pairs); CHECK_DEV(n_sparse);
+    TORCH_CHECK(buf.dtype() == torch::kUInt8 && offsets.dtype() == torch::kInt64
+                && egress.dtype() == torch::kUInt8);
+    TORCH_CHECK(sub_bitmap.dim() == 2 && sub_bitmap.size(0) == 256);
+    const int64_t M = offsets.size(0) - 1, W = sub_bitmap.size(1);
+    if (M <= 0) return;
+    TORCH_CHECK(uniform_len >= 0 && uniform_len < (int64_t(1) << 30));
+    const int64_t rec = (uniform_len + 16 + 15) & ~int64_t(15);
+    TORCH_CHECK(ring_bytes % 16 == 0 && n_users >= 0 && n_users <= W * 64
+                && ring_wpos.numel() >= n_users && ring_wpos.dtype() == torch::kInt64
+                && egress.numel() >= n_users * ring_bytes,
+                "rings do not cover n_users");
+    TORCH_CHECK(buf.numel() >= M * uniform_len, "batch shorter than M uniform messages");
+    check_flat_shape(pairs, rec / 16);
+    // the image kernel's unit index and the dense fan-out's 1-D grid
+    TORCH_CHECK(M * (rec / 16) < (int64_t(1) << 31)
+                && dense_grid_x((int32_t)n_users, DENSE_GROUP, dense_geom((int32_t)(rec / 16)).n_chunks)
+                       * k2b_blocks(M) < (int64_t(1) << 31),
+                "batch too large for the dense fan-out");
+    TORCH_CHECK(scratch64.dtype() == torch::kInt64 && scratch32.dtype() == torch::kInt32
+                && scratch64.is_contiguous() && scratch32.is_contiguous()
+                && (uintptr_t)scratch64.data_ptr<int64_t>() % 16 == 0
+                && scratch64.numel() >= uniform_tick_scratch64(M, W, rec / 16)
+                && scratch32.numel() >= uniform_tick_scratch32(M, W),
+                "fused tick scratch too small");
+    UniformTick t;
+    t.buf = buf.data_ptr<uint8_t>();
+    t.offsets = offsets.data_ptr<int64_t>();
+    t.M = (int32_t)M;
+    t.hash_seed = hash_seed;
+    t.sub_bitmap = (const uint64_t*)sub_bitmap.data_ptr<int64_t>();
+    t.W = (int32_t)W;
+    t.n_users = (int32_t)n_users;
+    t.ring_bytes = ring_bytes;
+    t.capacity = (int32_t)pairs.size(0);
+    t.uniform_len = (int32_t)uniform_len;
+    t.rec = (int32_t)rec;
+    t.seq_base = (uint32_t)seq_base;
+    t.ring_wpos = (uint64_t*)ring_wpos.data_ptr<int64_t>();
+    t.n_pairs = n_pairs.data_ptr<int32_t>();
+    t.n_sparse = n_sparse.data_ptr<int32_t>();
+    t.pairs = pair_ptr(pairs);
+    t.drops = (uint32_t*)drops.data_ptr<int32_t>();
+    t.scratch64 = scratch64.data_ptr<int64_t>();
+    t.scratch32 = scratch32.data_ptr<int32_t>();
+    t.egress = egress.data_ptr<uint8_t>();
+    t.nt = (int)nt;
+    t.dense = (int)dense;
+    launch_tick_uniform_broadcast(&t, cur_stream());
+}
+
+std::vector<int64_t> uniform_tick_scratch_sizes(int64_t M, int64_t W, int64_t rec) {
+    return {uniform_tick_scratch64(M, W, rec / 16), uniform_tick_scratch32(M, W)};
+}
+
+// Fused drain: one kernel copies the cursors to `staging` and zeroes them,
+// one async copy lands them in the engine's pinned `host` buffer, one stream
+// synchronise makes that buffer readable.
+void drain_cursors(torch::Tensor ring_wpos, torch::Tensor staging, torch::Tensor host) {
+    CHECK_DEV(ring_wpos); CHECK_CONTIG(ring_wpos); CHECK_DEV(staging); CHECK_CONTIG(staging);
+    TORCH_CHECK(!host.is_cuda() && host.is_pinned() && host.is_contiguous(),
+                "host must be a pinned CPU tensor");
+    TORCH_CHECK(ring_wpos.dtype() == torch::kInt64 && staging.dtype() == torch::kInt64
+                && host.dtype() == torch::kInt64);
+    const int64_t n = ring_wpos.numel();
+    TORCH_CHECK(staging.numel() >= n && host.numel() >= n && n <= INT32_MAX);
+    if (n == 0) return;
+    hipStream_t s = cur_stream();
+    launch_drain_cursors(ring_wpos.data_ptr<int64_t>(), staging.data_ptr<int64_t>(), (int32_t)n,
+                         s);
+    hipError_t e = hipMemcpyAsync(host.data_ptr<int64_t>(), staging.data_ptr<int64_t>(),
+                                  (size_t)n * 8, hipMemcpyDeviceToHost, s);
+    TORCH_CHECK(e == hipSuccess, "drain_cursors copy: ", hipGetErrorString(e));
+    e = hipStreamSynchronize(s);
+    TORCH_CHECK(e == hipSuccess, "drain_cursors sync: ", hipGetErrorString(e));
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("tick_uniform_broadcast", &tick_uniform_broadcast,
+          "fused uniform broadcast tick: K4, K2a, K2b tiles, dense + sparse fan-out");
+    m.def("uniform_tick_scratch_sizes", &uniform_tick_scratch_sizes,
+          "(int64, int32) scratch elements tick_uniform_broadcast needs for (M, W, rec)");
+    m.def("drain_cursors", &drain_cursors,
+          "fused drain: cursors -> pinned host buffer, cursors zeroed, stream synchronised",
+          py::call_guard<py::gil_scoped_release>());
     m.def("topic_mask_origin_t", &topic_mask_origin_t,
           "K2a transposed with per-message origin: remote-origin rows keep user bits only");
     m.def("emit_direct_peers", &emit_direct_peers,

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "../common/tick_geom.h"
+
 // A delivery pair as ONE 16-byte record {user, msg, ring dst}: emitters do a
 // single dword4 store per pair and K3 a single dword4 load per unit.  The
 // SoA layout (three arrays) cost ~3x scattered sub-line stores per pair —
@@ -27,6 +29,34 @@ struct ParseOut {
     int32_t* topics_cnt;
     uint64_t* recip_hash;
     uint64_t* timestamp;
+};
+
+// Everything one fused uniform broadcast tick needs.  All pointers are
+// device memory owned by the caller; the launcher allocates nothing and
+// never synchronises.
+struct UniformTick {
+    const uint8_t* buf;          // the ingested batch
+    const int64_t* offsets;      // [M+1] message starts (also K3's payload_off)
+    int32_t M;
+    uint64_t hash_seed;
+    const uint64_t* sub_bitmap;  // [256][W]
+    int32_t W;
+    int32_t n_users;
+    int64_t ring_bytes;
+    int32_t capacity;            // rows of pairs
+    int32_t uniform_len;         // wire bytes of every message
+    int32_t rec;                 // ring_rec(uniform_len)
+    uint32_t seq_base;
+    uint64_t* ring_wpos;         // [n_users]
+    int32_t* n_pairs;            // [1] pair slots claimed (zeroed by the tick)
+    int32_t* n_sparse;           // [1] pairs in the sparse list (zeroed by the tick)
+    PairRec* pairs;              // the sparse list
+    uint32_t* drops;
+    int64_t* scratch64;          // uniform_tick_scratch64(M, W, rec / 16) elements
+    int32_t* scratch32;          // uniform_tick_scratch32(M, W) elements
+    uint8_t* egress;
+    int nt;                      // non-temporal egress stores (flat fan-out)
+    int dense;                   // != 0: dense tiles go to the dense fan-out
 };
 
 extern "C" {
@@ -112,6 +142,13 @@ void launch_k6_direct_apply(uint64_t* table_keys, int32_t* table_vals, int64_t t
                             const uint64_t* up_keys, const int32_t* up_owners, int32_t n_up,
                             const uint64_t* del_keys, int32_t n_del, uint32_t* n_failed,
                             hipStream_t s);
+
+// Fused uniform broadcast tick: K4, K2a, K2b (tiles), the dense fan-out and
+// the flat fan-out over the sparse list, back to back on one stream.
+void launch_tick_uniform_broadcast(const UniformTick* t, hipStream_t s);
+
+// Drain: staging[i] = ring_wpos[i]; ring_wpos[i] = 0
+void launch_drain_cursors(int64_t* ring_wpos, int64_t* staging, int32_t n, hipStream_t s);
 
 // K7
 void launch_k7_compact_rings(const uint8_t* egress, int64_t ring_bytes, const int64_t* wpos,

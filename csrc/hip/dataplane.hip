@@ -46,6 +46,14 @@
 //   K6  k6_direct_apply — batched DirectMap upserts/deletes (CAS insert,
 //                        tombstoned values)
 //   K7  k7_compact_rings — gather used ring prefixes into one staging buffer
+//   fused uniform broadcast tick (launch_tick_uniform_broadcast, end of this
+//                        file) — the broadcast-only uniform shape as one
+//                        launcher call: K4, K2a, k2b_p1_count_z, k2b_p2_tiles
+//                        (P2 plus a dense / sparse sort of the (user, block)
+//                        tiles), k2b_p3_sparse (pairs for sparse tiles only),
+//                        k3d_image + k3_fanout_dense (dense tiles stored from
+//                        registers, no pair records) and the flat K3 over the
+//                        sparse list; k_drain_cursors is the fused drain
 //
 // Shared device building blocks, each defined once and force-inlined:
 //   store16<NT>        the only place the non-temporal store choice is made
@@ -788,6 +796,26 @@ void launch_k3_fanout_ref(const uint8_t* buf, const int64_t* payload_off,
 //          host-passed base would be frozen into the captured graph)
 // n_pairs is read from a device pointer and clamped to the buffer capacity.
 // ---------------------------------------------------------------------------
+// The 16 bytes a full-stride record holds at payload byte offset coff (a
+// multiple of 16) of the len-byte message at msg: the source bytes, zeros
+// past the message's end.  The one definition of those bytes: the flat
+// kernels call it per delivered unit, the dense fan-out once per image unit.
+__device__ __forceinline__ cdn_v4u payload_unit(const uint8_t* __restrict__ msg, int32_t coff,
+                                                int32_t len)
+{
+    const uint8_t* src = msg + coff;
+    if (coff + 16 <= len && (((uintptr_t)src) & 15) == 0) return *(const cdn_v4u*)src;
+    // pure pad unit: zeros, so the record stride is fully written
+    // (full-line NT writes, no RMW at record boundaries)
+    if (coff >= len) return cdn_v4u{0u, 0u, 0u, 0u};
+    // misaligned source or partial tail unit: zero-fill to one full 16 B store
+    uint8_t tmp[16];
+    #pragma unroll
+    for (int b = 0; b < 16; ++b) tmp[b] = (coff + b < len) ? src[b] : 0;
+    cdn_v4u v; memcpy(&v, tmp, 16);
+    return v;
+}
+
 template <int NT, bool SEQ_FROM_PTR>
 __global__ void __launch_bounds__(256) k3_fanout_flat_t(
     const uint8_t* __restrict__ buf,
@@ -825,22 +853,7 @@ __global__ void __launch_bounds__(256) k3_fanout_flat_t(
             store16<NT>(dst, cdn_v4u{(uint32_t)len, seq_base + (uint32_t)mi, 0u, 0u});
             continue;
         }
-        const uint8_t* src = buf + payload_off[mi] + (size_t)(unit - 1) * 16;
-        const int32_t coff = (unit - 1) * 16;
-        if (coff + 16 <= len && (((uintptr_t)src) & 15) == 0) {
-            store16<NT>(dst, *(const cdn_v4u*)src);
-        } else if (coff >= len) {
-            // pure pad unit: zero store so the record stride is fully
-            // written (full-line NT writes, no RMW at record boundaries)
-            store16<NT>(dst, cdn_v4u{0u, 0u, 0u, 0u});
-        } else {
-            // partial tail unit: zero-fill to one full 16 B store
-            uint8_t tmp[16];
-            #pragma unroll
-            for (int b = 0; b < 16; ++b) tmp[b] = (coff + b < len) ? src[b] : 0;
-            cdn_v4u v; memcpy(&v, tmp, 16);
-            store16<NT>(dst, v);
-        }
+        store16<NT>(dst, payload_unit(buf + payload_off[mi], (unit - 1) * 16, len));
     }
 }
 
@@ -1032,9 +1045,10 @@ void launch_k2a_topic_mask_t(const uint64_t* sub_bitmap, const uint8_t* buf,
 //       + per-block exclusive prefixes
 //   P3  per-(user, block) emission at precomputed offsets
 // ---------------------------------------------------------------------------
-#define K2B_BLK 32
+// (K2B_BLK, the block size, is in dataplane.h)
 
-extern "C" __global__ void k2b_p1_count(
+// P1 body, shared with the fused tick's k2b_p1_count_z.
+__device__ __forceinline__ void k2b_p1_body(
     const uint64_t* __restrict__ mask_t,   // [W][M]
     int32_t M, int32_t W, int32_t NB,
     int32_t* __restrict__ bcount)          // [NB][W*64]
@@ -1051,6 +1065,56 @@ extern "C" __global__ void k2b_p1_count(
     bcount[(int64_t)b * (W * 64) + (w * 64 + lane)] = c;
 }
 
+extern "C" __global__ void k2b_p1_count(
+    const uint64_t* __restrict__ mask_t, int32_t M, int32_t W, int32_t NB,
+    int32_t* __restrict__ bcount)
+{
+    k2b_p1_body(mask_t, M, W, NB, bcount);
+}
+
+// What P2 settles for one user (lane): the pair-slot base of its span, how
+// many records its ring still takes, and where the first of them goes.
+struct K2bUser { int32_t base; int32_t fit; int64_t dst; };
+
+// P2 body, shared by k2b_p2_bases and the fused tick's k2b_p2_tiles: per-user
+// totals and block prefixes, the wave-aggregated span claim, the closed-form
+// ring math (cursor advance) and the drop count.  Every lane of the wave
+// must call it (it shuffles); an inactive lane gets zeros back.
+__device__ __forceinline__ K2bUser k2b_p2_body(
+    const int32_t* __restrict__ bcount,    // [NB][W*64]
+    int u, bool active, int32_t W, int32_t NB,
+    int64_t ring_bytes, int32_t capacity, int32_t uniform_rec,
+    uint64_t* __restrict__ ring_wpos,
+    int32_t* __restrict__ n_pairs,
+    int32_t* __restrict__ pprefix,         // [NB][W*64] out: per-block p-offset
+    uint32_t* __restrict__ drops)
+{
+    const int lane = threadIdx.x & 63;
+    int total = 0;
+    if (active) {
+        for (int b = 0; b < NB; ++b) {
+            pprefix[(int64_t)b * (W * 64) + u] = total;
+            total += bcount[(int64_t)b * (W * 64) + u];
+        }
+    }
+    // the contiguous per-user span; inactive lanes carry total = 0 through it
+    K2bUser r{wave_claim_span(total, n_pairs), 0, 0};
+    uint32_t dropped = 0;
+    if (active) {
+        const uint64_t wpos = ring_wpos[u];
+        r.fit = (int32_t)((ring_bytes - wpos) / (uint64_t)uniform_rec);
+        r.dst = (int64_t)u * ring_bytes + (int64_t)wpos;
+        int cap_room = capacity - r.base; if (cap_room < 0) cap_room = 0;
+        int emitted = total; if (emitted > r.fit) emitted = r.fit; if (emitted > cap_room) emitted = cap_room;
+        ring_wpos[u] = wpos + (uint64_t)emitted * uniform_rec;
+        dropped = (uint32_t)(total - emitted);
+    }
+    // one drops atomic per wave
+    for (int d = 1; d < 64; d <<= 1) dropped += __shfl_down(dropped, d);
+    if (lane == 0 && dropped) atomicAdd(drops, dropped);
+    return r;
+}
+
 extern "C" __global__ void k2b_p2_bases(
     const int32_t* __restrict__ bcount,    // [NB][W*64]
     int32_t W, int32_t NB, int32_t n_users,
@@ -1065,31 +1129,13 @@ extern "C" __global__ void k2b_p2_bases(
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = u < n_users;
-    const int lane = threadIdx.x & 63;
-    int total = 0;
+    const K2bUser r = k2b_p2_body(bcount, u, active, W, NB, ring_bytes, capacity, uniform_rec,
+                                  ring_wpos, n_pairs, pprefix, drops);
     if (active) {
-        for (int b = 0; b < NB; ++b) {
-            pprefix[(int64_t)b * (W * 64) + u] = total;
-            total += bcount[(int64_t)b * (W * 64) + u];
-        }
+        ubase[u] = r.base;
+        ufit[u] = r.fit;
+        udst[u] = r.dst;
     }
-    // the contiguous per-user span; inactive lanes carry total = 0 through it
-    const int my_base = wave_claim_span(total, n_pairs);
-    uint32_t dropped = 0;
-    if (active) {
-        ubase[u] = my_base;
-        const uint64_t wpos = ring_wpos[u];
-        const int32_t fit = (int32_t)((ring_bytes - wpos) / (uint64_t)uniform_rec);
-        ufit[u] = fit;
-        udst[u] = (int64_t)u * ring_bytes + (int64_t)wpos;
-        int cap_room = capacity - my_base; if (cap_room < 0) cap_room = 0;
-        int emitted = total; if (emitted > fit) emitted = fit; if (emitted > cap_room) emitted = cap_room;
-        ring_wpos[u] = wpos + (uint64_t)emitted * uniform_rec;
-        dropped = (uint32_t)(total - emitted);
-    }
-    // one drops atomic per wave
-    for (int d = 1; d < 64; d <<= 1) dropped += __shfl_down(dropped, d);
-    if (lane == 0 && dropped) atomicAdd(drops, dropped);
 }
 
 extern "C" __global__ void k2b_p3_emit(
@@ -1449,6 +1495,285 @@ void launch_k6_direct_apply(uint64_t* table_keys, int32_t* table_vals, int64_t t
     hipLaunchKernelGGL(k6_direct_apply, dim3(blocks), dim3(threads), 0, s, table_keys,
                        table_vals, table_size, up_keys, up_owners, n_up, del_keys, n_del,
                        n_failed);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Fused uniform broadcast tick.  The broadcast-only uniform shape (every
+// message the same wire length, no Direct routing, no peer slots, no
+// by-reference records) runs as ONE launcher call:
+//
+//   K4  k4_parse_batch, K2a k2a_topic_mask_t   as everywhere, into scratch
+//   P1  k2b_p1_count_z   P1, and zeroes the tick's two counters
+//   P2  k2b_p2_tiles     P2 (same claims, cursors and drops), then sorts each
+//                        (user, 32-message block) TILE into dense or sparse
+//   P3  k2b_p3_sparse    pair records for the sparse tiles only
+//   K3d k3d_image + k3_fanout_dense   the dense tiles, from registers
+//   K3  k3_fanout_flat_t    the sparse list (flat2, as on the per-op path)
+//
+// A tile is DENSE when its user takes every message of the block and all of
+// them are delivered (they fit the ring and lie within pair capacity).  The
+// bytes such a tile puts into the ring are the block's records back to back
+// — the same bytes for every dense user — so k3d_image builds the tick's
+// record image once and K3d loads a chunk of it per workgroup and stores it
+// to one user after another: one store instruction per KiB and nothing else
+// in the loop, where the flat kernel spends a pair load, an offset load, a
+// source load and a division per 16 bytes of every delivery.  No pair
+// record is written for a dense tile; tdst[b][u] holds its ring address
+// (-1: not dense).
+//
+// Every other tile's deliverable pairs go to the SPARSE list: pairs[0 ..
+// *n_sparse), grouped by user with messages in order like P3's list, but
+// without placeholders (an undeliverable pair is only counted, in P2).  A
+// user's pairs start at usbase[u] + tslot[b][u]; P2 claims the spans with a
+// second wave_claim_span, so P3 needs no atomics.  The list can never
+// outgrow the pair buffer: a pair is deliverable only if its slot in P2's
+// claim order is below capacity, so there are at most capacity of them.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void k2b_p1_count_z(
+    const uint64_t* __restrict__ mask_t, int32_t M, int32_t W, int32_t NB,
+    int32_t* __restrict__ bcount, int32_t* __restrict__ n_pairs, int32_t* __restrict__ n_sparse)
+{
+    // read next by P2, a later launch on the same stream
+    if (blockIdx.x == 0 && threadIdx.x == 0) { *n_pairs = 0; *n_sparse = 0; }
+    k2b_p1_body(mask_t, M, W, NB, bcount);
+}
+
+extern "C" __global__ void k2b_p2_tiles(
+    const int32_t* __restrict__ bcount,    // [NB][W*64]
+    int32_t M, int32_t W, int32_t NB, int32_t n_users,
+    int64_t ring_bytes, int32_t capacity, int32_t uniform_rec, int32_t use_dense,
+    uint64_t* __restrict__ ring_wpos,
+    int32_t* __restrict__ n_pairs,
+    int32_t* __restrict__ n_sparse,
+    int32_t* __restrict__ pprefix,         // [NB][W*64] out: per-block p-offset
+    int32_t* __restrict__ tslot,           // [NB][W*64] out: sparse slot, relative to usbase
+    int64_t* __restrict__ tdst,            // [NB][W*64] out: dense tile ring address, or -1
+    int32_t* __restrict__ ulim,            // [W*64] out: records delivered at most
+    int32_t* __restrict__ usbase,          // [W*64] out: first sparse-list slot
+    int64_t* __restrict__ udst,            // [W*64] out: ring dst base
+    uint32_t* __restrict__ drops)
+{
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = u < n_users;
+    const K2bUser r = k2b_p2_body(bcount, u, active, W, NB, ring_bytes, capacity, uniform_rec,
+                                  ring_wpos, n_pairs, pprefix, drops);
+    int cap_room = capacity - r.base; if (cap_room < 0) cap_room = 0;
+    const int lim = r.fit < cap_room ? r.fit : cap_room;
+    int n_sp = 0;
+    if (active) {
+        int p = 0;
+        for (int b = 0; b < NB; ++b) {
+            const int64_t i = (int64_t)b * (W * 64) + u;
+            const int cnt = bcount[i];
+            const int nm = min(M - b * K2B_BLK, K2B_BLK);
+            const bool dense = use_dense && cnt == nm && p + cnt <= lim;
+            tdst[i] = dense ? r.dst + (int64_t)p * uniform_rec : -1;
+            tslot[i] = n_sp;
+            if (!dense) n_sp += max(0, min(cnt, lim - p));
+            p += cnt;
+        }
+    }
+    const int sbase = wave_claim_span(n_sp, n_sparse);
+    if (active) {
+        ulim[u] = lim;
+        usbase[u] = sbase;
+        udst[u] = r.dst;
+    }
+}
+
+// One wave per (mask word, block), like P3.  Each lane first looks at its own
+// user's tile; the wave then takes the sparse tiles one at a time with lanes
+// spread over the block's MESSAGES, so a tile's pairs are stored side by
+// side (ballot + popcount give the slot) and not one lane per user at a
+// 4 KiB stride.  All tiles dense or empty: the wave leaves after the ballot.
+extern "C" __global__ void k2b_p3_sparse(
+    const uint64_t* __restrict__ mask_t,   // [W][M]
+    const int32_t* __restrict__ bcount,
+    const int32_t* __restrict__ pprefix,
+    const int32_t* __restrict__ tslot,
+    const int64_t* __restrict__ tdst,
+    const int32_t* __restrict__ ulim,
+    const int32_t* __restrict__ usbase,
+    const int64_t* __restrict__ udst,
+    int32_t M, int32_t W, int32_t NB, int32_t n_users, int32_t uniform_rec,
+    PairRec* __restrict__ pairs)
+{
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (wave >= W * NB) return;
+    const int w = wave / NB, b = wave - (wave / NB) * NB;
+    const int lane = threadIdx.x & 63;
+    const int u = w * 64 + lane;
+    int p0 = 0, lim = 0, slot0 = 0;
+    int64_t dstb = 0;
+    bool sparse = false;
+    if (u < n_users) {
+        const int64_t i = (int64_t)b * (W * 64) + u;
+        p0 = pprefix[i];
+        lim = ulim[u];
+        sparse = tdst[i] < 0 && bcount[i] > 0 && p0 < lim;
+        slot0 = usbase[u] + tslot[i];
+        dstb = udst[u];
+    }
+    unsigned long long todo = __ballot(sparse);
+    if (!todo) return;
+    const int m0 = b * K2B_BLK, nm = min(M - m0, K2B_BLK);
+    const uint64_t word = lane < nm ? mask_t[(int64_t)w * M + m0 + lane] : 0ull;
+    while (todo) {
+        const int j = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int jp0 = __shfl(p0, j), jlim = __shfl(lim, j), jslot = __shfl(slot0, j);
+        const int64_t jdst = ((int64_t)__shfl((int)(dstb >> 32), j) << 32)
+                             | (uint32_t)__shfl((int)dstb, j);
+        const bool bit = (word >> j) & 1ull;
+        const unsigned long long mb = __ballot(bit);
+        const int rank = __popcll(mb & ((1ull << lane) - 1ull));
+        const int p = jp0 + rank;
+        if (bit && p < jlim)
+            store_pair(pairs + jslot + rank, w * 64 + j, m0 + lane,
+                       jdst + (int64_t)p * uniform_rec);
+    }
+}
+
+// The record image: the M records of this tick, back to back at full stride,
+// exactly the bytes the flat kernel stores for each of them — header
+// {len, seq_base + m, 0, 0}, then payload_unit values.  One thread per unit,
+// so a misaligned source or a partial tail is handled once per image unit
+// and not once per delivery; K3d then only does aligned dword4 loads.
+extern "C" __global__ void k3d_image(
+    const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ offsets,   // [M+1]
+    int32_t M, int32_t units_per_rec, uint32_t div_magic, int32_t div_shift,
+    int32_t uniform_len, uint32_t seq_base,
+    cdn_v4u* __restrict__ image)           // [M * units_per_rec]
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)(M * units_per_rec)) return;
+    const int m = (int)(((uint64_t)i * div_magic) >> div_shift);
+    const int q = (int)i - m * units_per_rec;
+    image[i] = q == 0 ? cdn_v4u{(uint32_t)uniform_len, seq_base + (uint32_t)m, 0u, 0u}
+                      : payload_unit(buf + offsets[m], (q - 1) * 16, uniform_len);
+}
+
+// K3d.  blockIdx.x = (group * NB + block) * n_chunks + chunk: a workgroup
+// loads units [chunk * chunk_units, + chunk_units) of the block's part of the
+// image (dense_geom) into registers and then walks `group` consecutive
+// users, storing the chunk to each dense one.  The user index, the density
+// test and the address are wave-uniform.  Neighbouring workgroups write
+// neighbouring spans of the same users' rings.  Stores are plain at either
+// nt_fanout setting: on the bench's layout this shape measured 510 us plain
+// against 540 us non-temporal (profiles/k3_write_shapes.txt), the opposite
+// of the flat kernel.
+__global__ void __launch_bounds__(DENSE_THREADS) k3_fanout_dense(
+    const cdn_v4u* __restrict__ image,     // [M * units_per_rec]
+    const int64_t* __restrict__ tdst,      // [NB][users64]
+    int32_t M, int32_t NB, int32_t users64, int32_t n_users, int32_t units_per_rec,
+    int32_t n_chunks, int32_t chunk_units, int32_t group,
+    uint8_t* __restrict__ egress)
+{
+    const int per_group = NB * n_chunks;
+    const int g = blockIdx.x / per_group, bc = blockIdx.x - g * per_group;
+    const int b = bc / n_chunks, c = bc - b * n_chunks;
+    const int m0 = b * K2B_BLK, nm = min(M - m0, K2B_BLK);
+    const int lo = c * chunk_units + (int)threadIdx.x;
+    const int hi = min(nm * units_per_rec, (c + 1) * chunk_units);
+    if (lo >= hi) return;
+    const cdn_v4u* __restrict__ img = image + (size_t)m0 * units_per_rec;
+    cdn_v4u v[DENSE_MAX_V];
+    #pragma unroll
+    for (int k = 0; k < DENSE_MAX_V; ++k) {
+        const int unit = lo + k * DENSE_THREADS;
+        v[k] = unit < hi ? img[unit] : cdn_v4u{0u, 0u, 0u, 0u};
+    }
+    const int64_t* __restrict__ trow = tdst + (int64_t)b * users64;
+    const int u1 = min(n_users, (g + 1) * group);
+    for (int u = g * group; u < u1; ++u) {
+        const int64_t d = trow[u];
+        if (d < 0) continue;
+        uint8_t* dst = egress + d + (size_t)lo * 16;
+        #pragma unroll
+        for (int k = 0; k < DENSE_MAX_V; ++k)
+            if (lo + k * DENSE_THREADS < hi)
+                store16<0>(dst + (size_t)k * (DENSE_THREADS * 16), v[k]);
+    }
+}
+
+extern "C" __global__ void k_drain_cursors(int64_t* __restrict__ ring_wpos,
+                                           int64_t* __restrict__ staging, int32_t n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    staging[i] = ring_wpos[i];
+    ring_wpos[i] = 0;
+}
+
+extern "C" {
+
+void launch_tick_uniform_broadcast(const UniformTick* t, hipStream_t s) {
+    const int32_t M = t->M, W = t->W;
+    if (M <= 0) return;
+    const int32_t NB = (int32_t)k2b_blocks(M);
+    const int64_t U = (int64_t)W * 64, T = (int64_t)NB * U;
+    // carve the scratch (sizes: uniform_tick_scratch64 / 32 in dataplane.h)
+    const int32_t units = t->rec / 16;
+    int64_t* p64 = t->scratch64;
+    cdn_v4u* image = (cdn_v4u*)p64;  p64 += 2 * (int64_t)M * units;  // first: 16-aligned
+    int64_t* payload_off = p64;  p64 += M;
+    int64_t* topics_off = p64;   p64 += M;
+    int64_t* recip_hash = p64;   p64 += M;
+    int64_t* timestamp = p64;    p64 += M;
+    uint64_t* mask_t = (uint64_t*)p64;  p64 += (int64_t)W * M;
+    int64_t* tdst = p64;         p64 += T;
+    int64_t* udst = p64;
+    int32_t* p32 = t->scratch32;
+    int32_t* disc = p32;         p32 += M;
+    int32_t* payload_len = p32;  p32 += M;
+    int32_t* topics_cnt = p32;   p32 += M;
+    int32_t* bcount = p32;       p32 += T;
+    int32_t* pprefix = p32;      p32 += T;
+    int32_t* tslot = p32;        p32 += T;
+    int32_t* ulim = p32;         p32 += U;
+    int32_t* usbase = p32;
+
+    launch_k4_parse(t->buf, t->offsets, M, t->hash_seed,
+                    ParseOut{disc, payload_off, payload_len, topics_off, topics_cnt,
+                             (uint64_t*)recip_hash, (uint64_t*)timestamp}, s);
+    launch_k2a_topic_mask_t(t->sub_bitmap, t->buf, topics_off, topics_cnt, disc, mask_t, M, W, s);
+
+    const int threads = 256;
+    const int blocks_wb = (W * NB * 64 + threads - 1) / threads;
+    const int blocks_u = (t->n_users + threads - 1) / threads;
+    hipLaunchKernelGGL(k2b_p1_count_z, dim3(blocks_wb), dim3(threads), 0, s, mask_t, M, W, NB,
+                       bcount, t->n_pairs, t->n_sparse);
+    hipLaunchKernelGGL(k2b_p2_tiles, dim3(blocks_u), dim3(threads), 0, s, bcount, M, W, NB,
+                       t->n_users, t->ring_bytes, t->capacity, t->rec, t->dense ? 1 : 0,
+                       t->ring_wpos, t->n_pairs, t->n_sparse, pprefix, tslot, tdst, ulim, usbase,
+                       udst, t->drops);
+    hipLaunchKernelGGL(k2b_p3_sparse, dim3(blocks_wb), dim3(threads), 0, s, mask_t, bcount,
+                       pprefix, tslot, tdst, ulim, usbase, udst, M, W, NB, t->n_users, t->rec,
+                       t->pairs);
+    if (t->dense) {
+        const DenseGeom geo = dense_geom(units);
+        uint32_t dm; int32_t dsh;
+        u32_div_magic(units, &dm, &dsh);
+        hipLaunchKernelGGL(k3d_image, dim3((M * units + threads - 1) / threads), dim3(threads),
+                           0, s, t->buf, t->offsets, M, units, dm, dsh, t->uniform_len,
+                           t->seq_base, image);
+        const dim3 grid((uint32_t)(dense_grid_x(t->n_users, DENSE_GROUP, geo.n_chunks) * NB));
+        hipLaunchKernelGGL(k3_fanout_dense, grid, dim3(DENSE_THREADS), 0, s, image, tdst, M, NB,
+                           (int32_t)U, t->n_users, units, geo.n_chunks, geo.chunk_units,
+                           DENSE_GROUP, t->egress);
+    }
+    // the sparse list: offsets is payload_off (fanout_wire), the length a scalar
+    launch_flat<false>(t->buf, t->offsets, payload_len, t->pairs, t->seq_base, nullptr,
+                       t->n_sparse, t->capacity, units, t->uniform_len, t->egress, t->nt, 0, s);
+}
+
+void launch_drain_cursors(int64_t* ring_wpos, int64_t* staging, int32_t n, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_drain_cursors, dim3((n + 255) / 256), dim3(256), 0, s, ring_wpos,
+                       staging, n);
 }
 
 }  // extern "C"

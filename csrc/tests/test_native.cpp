@@ -3,6 +3,7 @@
 // reference's safety posture (#![forbid(unsafe_code)] + clippy lanes,
 // "plan TSan/ASan CI lanes" for the C++ rewrite).
 
+#include <algorithm>
 #include <cassert>
 #include <cstdio>
 #include <cstring>
@@ -12,6 +13,7 @@
 
 #include "../bls/bls.h"
 #include "../common/divmagic.h"
+#include "../common/tick_geom.h"
 #include "../net/pump.h"
 #include "../net/udp_stream.h"
 #include "../state/versioned_map.h"
@@ -565,7 +567,51 @@ static int test_u32_div_magic_exact() {
     return 0;
 }
 
+// tick_geom.h: for every record size the fused tick serves (16 B units,
+// 2 .. 256 per record) the dense fan-out's chunks must cover a full block's
+// image exactly once, each within the per-thread register budget and a whole
+// number of waves; the grid must cover every user; the scratch carving in
+// launch_tick_uniform_broadcast must fit the sizes the engine allocates.
+static int test_tick_geometry() {
+    for (int32_t units = 1; units <= 257; ++units) {
+        const DenseGeom g = dense_geom(units);
+        const int32_t image = units * K2B_BLK;
+        CHECK(g.n_chunks >= 1 && g.chunk_units >= 64 && g.chunk_units % 64 == 0);
+        CHECK(g.chunk_units <= DENSE_THREADS * DENSE_MAX_V);
+        CHECK((int64_t)g.n_chunks * g.chunk_units >= image);            // covers the image
+        CHECK((int64_t)(g.n_chunks - 1) * g.chunk_units < image);       // no empty chunk
+        // a partial block's image is a prefix: its chunks are a prefix too
+        for (int32_t nm : {1, 31}) {
+            int64_t covered = 0;
+            for (int32_t c = 0; c < g.n_chunks; ++c) {
+                const int64_t lo = (int64_t)c * g.chunk_units;
+                const int64_t hi = std::min<int64_t>((int64_t)nm * units, lo + g.chunk_units);
+                if (hi > lo) covered += hi - lo;
+            }
+            CHECK(covered == (int64_t)nm * units);
+        }
+    }
+    CHECK(dense_geom(70).n_chunks == 2 && dense_geom(70).chunk_units == 1152);  // 1 KiB bench
+    CHECK(dense_geom(256).n_chunks == 4 && dense_geom(256).chunk_units == 2048);
+    CHECK(dense_geom(2).n_chunks == 1 && dense_geom(2).chunk_units == 64);
+    for (int32_t n : {1, 31, 32, 33, 64, 130, 10000})
+        for (int32_t group : {8, 32})
+            for (int32_t nc : {1, 2, 4}) {
+                const int64_t gx = dense_grid_x(n, group, nc);
+                CHECK(gx % nc == 0 && gx / nc * group >= n && (gx / nc - 1) * group < n);
+            }
+    CHECK(k2b_blocks(1) == 1 && k2b_blocks(32) == 1 && k2b_blocks(33) == 2 && k2b_blocks(256) == 8);
+    for (int64_t M : {1, 32, 33, 70, 256})
+        for (int64_t W : {1, 3, 157}) {
+            const int64_t U = W * 64, T = k2b_blocks(M) * U;
+            CHECK(uniform_tick_scratch64(M, W, 70) == 4 * M + W * M + T + U + M * 1120 / 8);
+            CHECK(uniform_tick_scratch32(M, W) == 3 * M + 3 * T + 2 * U);
+        }
+    return 0;
+}
+
 int main() {
+    if (test_tick_geometry()) return 1;
     if (test_u32_div_magic_exact()) return 1;
     if (test_wire_roundtrip()) return 1;
     if (test_wire_fuzz_no_crash()) return 1;

@@ -83,6 +83,7 @@ class GpuBrokerEngine:
         hash_seed: int = 0,
         n_peer_slots: int = 0,
         ref_threshold: Optional[int] = None,
+        fused_tick: bool = True,
     ) -> None:
         # n_peer_slots (P): peer brokers as recipients of the device
         # pipeline.  The recipient index space is R = n_users + P; peer slot
@@ -112,6 +113,11 @@ class GpuBrokerEngine:
             "must stay below 2^31")
         self.nt_fanout = nt_fanout
         self.direct_enabled = direct_enabled
+        # fused_tick: a uniform broadcast-only tick (see _fused_tick_ok) runs
+        # as one native call, and drain_cursors as one; False keeps the
+        # per-op path everywhere.  fused_ticks counts the ticks that took it.
+        self.fused_tick = fused_tick
+        self.fused_ticks = 0
         # hash_seed keys the routing hash (keyhash.derive_routing_seed from
         # the cluster private key in live services): without it FNV-1a
         # collisions are offline-grindable and a crafted pubkey could siphon
@@ -179,6 +185,11 @@ class GpuBrokerEngine:
             self._drops = torch.zeros(1, **o32)
             self._n_pairs = torch.zeros(1, **o32)
             self._seq_dev = torch.zeros(1, **o32)  # device seq counter (graph path)
+            # fused tick: length of the sparse pair list of the last tick
+            self._n_sparse = torch.zeros(1, **o32)
+            self._dense_fanout = True
+            self._fused_scratch = None
+            self._drain_bufs = None
             self._graphs: Dict[Tuple[int, int, int], object] = {}
 
     # ---------------- subscription management (host-driven) ----------------
@@ -526,11 +537,43 @@ class GpuBrokerEngine:
                 self._pairs, self._drops, self._n_pairs, rec,
             )
 
+    def _fused_tick_ok(self, uniform_wire_len: Optional[int], origin) -> bool:
+        """The shape the fused native tick serves: uniform wire records that
+        the flat fan-out takes, broadcast only, one broker, all inline."""
+        return (self.fused_tick and self.fanout_wire and uniform_wire_len is not None
+                and not self.direct_enabled and self.n_peer_slots == 0
+                and origin is None and self.ref_threshold is None
+                and ring_rec(uniform_wire_len) <= self._flat_max_rec)
+
+    def _tick_fused(self, buf: torch.Tensor, offsets: torch.Tensor,
+                    uniform_wire_len: int, M: int) -> TickStats:
+        ops = self._ops
+        # engine-owned scratch, grown to the largest shape seen so far
+        n64, n32 = ops.uniform_tick_scratch_sizes(M, self.W, ring_rec(uniform_wire_len))
+        s64, s32 = self._fused_scratch or (None, None)
+        if s64 is None or s64.numel() < n64 or s32.numel() < n32:
+            s64 = torch.empty(max(n64, 0 if s64 is None else s64.numel()),
+                              dtype=torch.int64, device=self.device)
+            s32 = torch.empty(max(n32, 0 if s32 is None else s32.numel()),
+                              dtype=torch.int32, device=self.device)
+            self._fused_scratch = (s64, s32)
+        seq_base = self.seq
+        self.seq += M
+        ops.tick_uniform_broadcast(
+            buf, offsets, self.hash_seed, self.sub_bitmap, self.ring_wpos, self.ring_bytes,
+            self.n_recipients, self._pairs, self._drops, self._n_pairs, self._n_sparse,
+            s64, s32, uniform_wire_len, seq_base, self.egress,
+            1 if self.nt_fanout else 0, 1 if self._dense_fanout else 0)
+        self.fused_ticks += 1
+        return TickStats(n_messages=M)
+
     def _tick_gpu(self, buf: torch.Tensor, offsets: torch.Tensor,
                   uniform_wire_len: Optional[int] = None, origin=None,
                   ref_base: int = 0) -> TickStats:
         ops = self._ops
         M = offsets.shape[0] - 1
+        if M > 0 and self._fused_tick_ok(uniform_wire_len, origin):
+            return self._tick_fused(buf, offsets, uniform_wire_len, M)
         disc, payload_off, payload_len, topics_off, topics_cnt, recip_hash, _ts = ops.parse_batch(
             buf, offsets, self.hash_seed
         )
@@ -708,6 +751,15 @@ class GpuBrokerEngine:
         Retained by-reference batches are discarded: the cursors were the
         only way to reach the records that point into them."""
         self._discard_ref_batches()
+        if self.fused_tick and self.use_gpu_ops and self.is_cuda:
+            if self._drain_bufs is None:
+                self._drain_bufs = (
+                    torch.empty_like(self.ring_wpos),
+                    torch.empty(self.ring_wpos.shape, dtype=torch.int64, pin_memory=True),
+                )
+            staging, host = self._drain_bufs
+            self._ops.drain_cursors(self.ring_wpos, staging, host)  # synchronises
+            return host.clone()
         wpos = self.ring_wpos.detach().clone().to("cpu")
         self.ring_wpos.zero_()
         return wpos
