@@ -2,9 +2,14 @@
 // (csrc/hip/dataplane.hip). PyTorch owns every HBM buffer; these calls
 // invoke the extern "C" launchers defined next to the kernels and declared
 // in csrc/hip/dataplane.h and csrc/hip/bls_kernels.h.
+//
+// This file is the native boundary: the only place where a Python tensor
+// becomes a raw pointer.  Every op below is an `Op` (the checks), a list of
+// (tensor, element type, length) reads through Op::ptr, and one launch.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/core/DeviceGuard.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -12,18 +17,119 @@
 #include "hip/bls_kernels.h"
 #include "hip/dataplane.h"
 
-#define CHECK_DEV(x) TORCH_CHECK(x.is_cuda(), #x " must be on the GPU")
-#define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
+// The torch element type that stores a kernel-side T: the kernels read int64
+// storage as u64 words and int32 storage as u32 words or as PairRec rows.
+template <typename T> struct Stored { using type = T; };
+template <> struct Stored<uint64_t> { using type = int64_t; };
+template <> struct Stored<uint32_t> { using type = int32_t; };
+template <> struct Stored<PairRec> { using type = int32_t; };  // [cap][4], see Op::pairs
 
-static inline PairRec* pair_ptr(torch::Tensor& pairs) {
-    TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 4 && pairs.dtype() == torch::kInt32
-                && pairs.is_contiguous(), "pairs must be a contiguous int32 [cap, 4] tensor");
-    return (PairRec*)pairs.data_ptr<int32_t>();
-}
+// The shape an op states for an argument; -1 leaves a field open.
+struct Shape { int64_t dim = -1, rows = -1, cols = -1; };
+static constexpr Shape vec() { return {1, -1, -1}; }
+static constexpr Shape mat(int64_t rows = -1, int64_t cols = -1) { return {2, rows, cols}; }
 
-static inline hipStream_t cur_stream() {
-    return at::hip::getCurrentHIPStream().stream();
-}
+// One op's argument checks.  ptr() vets a tensor (dtype, stated shape,
+// contiguity, minimum length) and hands out its pointer; i32() narrows a
+// size or scalar.  Neither needs a GPU.  begin() then makes the device checks
+// for every tensor seen so far, in argument order, so a machine without a GPU
+// still exercises everything before them, and switches to the first tensor's
+// device for the rest of the op.  launched() looks at the launch result.
+// The tensors passed to ptr() must outlive the Op (they are the op's named
+// arguments and locals, never temporaries).
+class Op {
+public:
+    enum Where { kDevice, kPinnedHost };
+
+    explicit Op(const char* name) : name_(name) {}
+
+    template <typename T>
+    T* ptr(const torch::Tensor& t, const char* arg, int64_t min_numel = 0, Shape shape = {},
+           Where where = kDevice) {
+        using S = typename Stored<T>::type;
+        constexpr auto want = c10::CppTypeToScalarType<S>::value;
+        TORCH_CHECK(t.scalar_type() == want, name_, ": ", arg, " must be ", c10::toString(want),
+                    ", got ", c10::toString(t.scalar_type()));
+        TORCH_CHECK(shape.dim < 0 || t.dim() == shape.dim, name_, ": ", arg, " must have ",
+                    shape.dim, " dimension(s), got sizes ", t.sizes());
+        TORCH_CHECK((shape.rows < 0 || t.size(0) == shape.rows)
+                    && (shape.cols < 0 || t.size(1) == shape.cols),
+                    name_, ": ", arg, " must be [", shape.rows, ", ", shape.cols,
+                    "] (-1: any), got sizes ", t.sizes());
+        TORCH_CHECK(t.is_contiguous(), name_, ": ", arg, " must be contiguous, got sizes ",
+                    t.sizes(), " with strides ", t.strides());
+        TORCH_CHECK(t.numel() >= min_numel, name_, ": ", arg, " needs at least ", min_numel,
+                    " elements, got ", t.numel());
+        TORCH_CHECK(n_seen_ < kMaxSeen, name_, ": too many tensor arguments");
+        seen_[n_seen_++] = {arg, &t, where};
+        return reinterpret_cast<T*>(t.data_ptr<S>());
+    }
+
+    // ptr() for an argument that has exactly n elements; `per` says which
+    // argument's length sets n ("one per disc").
+    template <typename T>
+    T* same(const torch::Tensor& t, const char* arg, int64_t n, const char* per,
+            Shape shape = {}) {
+        T* p = ptr<T>(t, arg, n, shape);
+        TORCH_CHECK(t.numel() == n, name_, ": ", arg, " must have exactly ", n, " elements (",
+                    per, "), got ", t.numel());
+        return p;
+    }
+
+    PairRec* pairs(const torch::Tensor& t, const char* arg = "pairs") {
+        return ptr<PairRec>(t, arg, 0, mat(-1, 4));
+    }
+
+    // The one narrowing of a size or scalar to 32 bits.
+    int32_t i32(int64_t v, const char* what, int64_t lo = 0, int64_t hi = INT32_MAX) const {
+        TORCH_CHECK(v >= lo && v <= hi, name_, ": ", what, " = ", v, " is outside [", lo, ", ",
+                    hi, "]");
+        return (int32_t)v;
+    }
+
+    void ring_bytes(int64_t v) const {
+        TORCH_CHECK(v >= 0 && v % 16 == 0, name_, ": ring_bytes = ", v,
+                    " must be a non-negative multiple of 16");
+    }
+
+    // Device checks, last on purpose; returns the stream to launch on.
+    hipStream_t begin() {
+        TORCH_CHECK(n_seen_ > 0, name_, ": no tensor argument");
+        const c10::Device dev = seen_[0].t->device();
+        for (int i = 0; i < n_seen_; ++i) {
+            const torch::Tensor& t = *seen_[i].t;
+            if (seen_[i].where == kPinnedHost) {
+                TORCH_CHECK(!t.is_cuda() && t.is_pinned(), name_, ": ", seen_[i].arg,
+                            " must be a pinned CPU tensor, got one on ", t.device());
+                continue;
+            }
+            TORCH_CHECK(t.is_cuda(), name_, ": ", seen_[i].arg, " must be on a GPU, got ",
+                        t.device());
+            TORCH_CHECK(t.device() == dev, name_, ": ", seen_[i].arg, " is on ", t.device(),
+                        " but ", seen_[0].arg, " is on ", dev);
+        }
+        guard_.reset_device(dev);
+        return at::hip::getCurrentHIPStream().stream();
+    }
+
+    // After each launcher call.  Reads the launch error only: no
+    // synchronisation, so it is safe under stream capture.
+    void launched() const { check(hipGetLastError(), "kernel launch"); }
+
+    void check(hipError_t e, const char* what) const {
+        TORCH_CHECK(e == hipSuccess, name_, ": ", what, " failed: ", hipGetErrorString(e));
+    }
+
+    const char* name() const { return name_; }
+
+private:
+    struct Seen { const char* arg; const torch::Tensor* t; Where where; };
+    static constexpr int kMaxSeen = 16;
+    const char* name_;
+    Seen seen_[kMaxSeen];
+    int n_seen_ = 0;
+    c10::OptionalDeviceGuard guard_;
+};
 
 // Options for a new tensor of `dtype` on the device of `like`.
 static inline torch::TensorOptions opts(torch::ScalarType dtype, const torch::Tensor& like) {
@@ -44,10 +150,11 @@ static inline void check_flat_shape(const torch::Tensor& pairs, int64_t units_pe
 
 std::vector<torch::Tensor> parse_batch(torch::Tensor buf, torch::Tensor offsets,
                                        uint64_t hash_seed) {
-    CHECK_DEV(buf); CHECK_CONTIG(buf); CHECK_DEV(offsets); CHECK_CONTIG(offsets);
-    TORCH_CHECK(buf.dtype() == torch::kUInt8 && offsets.dtype() == torch::kInt64);
-    int32_t M = (int32_t)offsets.size(0) - 1;
-    TORCH_CHECK(M >= 0);
+    Op a("parse_batch");
+    const uint8_t* b = a.ptr<uint8_t>(buf, "buf");
+    const int64_t* off = a.ptr<int64_t>(offsets, "offsets", 1);
+    const int32_t M = a.i32(offsets.numel() - 1, "M");
+    hipStream_t s = a.begin();
     auto o32 = opts(torch::kInt32, buf);
     auto o64 = opts(torch::kInt64, buf);
     auto disc = torch::empty({M}, o32);
@@ -58,63 +165,83 @@ std::vector<torch::Tensor> parse_batch(torch::Tensor buf, torch::Tensor offsets,
     auto recip_hash = torch::empty({M}, o64);  // bit-cast u64
     auto timestamp = torch::empty({M}, o64);
     if (M > 0) {
-        ParseOut out{disc.data_ptr<int32_t>(), payload_off.data_ptr<int64_t>(),
-                     payload_len.data_ptr<int32_t>(), topics_off.data_ptr<int64_t>(),
-                     topics_cnt.data_ptr<int32_t>(),
-                     (uint64_t*)recip_hash.data_ptr<int64_t>(),
-                     (uint64_t*)timestamp.data_ptr<int64_t>()};
-        launch_k4_parse(buf.data_ptr<uint8_t>(), offsets.data_ptr<int64_t>(), M, hash_seed,
-                        out, cur_stream());
+        ParseOut out{a.ptr<int32_t>(disc, "disc"), a.ptr<int64_t>(payload_off, "payload_off"),
+                     a.ptr<int32_t>(payload_len, "payload_len"),
+                     a.ptr<int64_t>(topics_off, "topics_off"),
+                     a.ptr<int32_t>(topics_cnt, "topics_cnt"),
+                     a.ptr<uint64_t>(recip_hash, "recip_hash"),
+                     a.ptr<uint64_t>(timestamp, "timestamp")};
+        launch_k4_parse(b, off, M, hash_seed, out, s);
+        a.launched();
     }
     return {disc, payload_off, payload_len, topics_off, topics_cnt, recip_hash, timestamp};
 }
 
-// Shared part of the three K2a wrappers: M and W from disc and the bitmap,
-// the mask allocation ([M][W], or [W][M] when transposed) and the M > 0
-// guard around launch(mask, M, W).  Each wrapper does its own checks first.
-template <typename Launch>
-static torch::Tensor k2a_mask(const torch::Tensor& sub_bitmap, const torch::Tensor& buf,
-                              const torch::Tensor& disc, bool transposed, Launch launch) {
-    int32_t W = (int32_t)sub_bitmap.size(1);
-    int32_t M = (int32_t)disc.size(0);
-    auto mask = transposed ? torch::empty({(int64_t)W, M}, opts(torch::kInt64, buf))
-                           : torch::empty({M, (int64_t)W}, opts(torch::kInt64, buf));
-    if (M > 0) launch((uint64_t*)mask.data_ptr<int64_t>(), M, W);
-    return mask;
+// What the K2a ops and K2c share: the [256][W] bitmap, the batch and the
+// three per-message columns parse_batch made.  M is disc's length.
+struct TopicArgs {
+    uint64_t* sub_bitmap;
+    const uint8_t* buf;
+    const int64_t* topics_off;
+    const int32_t* topics_cnt;
+    const int32_t* disc;
+    int32_t M, W;
+};
+
+static TopicArgs topic_args(Op& a, const torch::Tensor& sub_bitmap, const torch::Tensor& buf,
+                            const torch::Tensor& topics_off, const torch::Tensor& topics_cnt,
+                            const torch::Tensor& disc) {
+    TopicArgs t;
+    t.sub_bitmap = a.ptr<uint64_t>(sub_bitmap, "sub_bitmap", 0, mat(256, -1));
+    t.buf = a.ptr<uint8_t>(buf, "buf");
+    t.disc = a.ptr<int32_t>(disc, "disc");
+    t.topics_off = a.same<int64_t>(topics_off, "topics_off", disc.numel(), "one per disc");
+    t.topics_cnt = a.same<int32_t>(topics_cnt, "topics_cnt", disc.numel(), "one per disc");
+    t.M = a.i32(disc.numel(), "M");
+    t.W = a.i32(sub_bitmap.size(1), "W");
+    return t;
 }
 
 torch::Tensor topic_mask(torch::Tensor sub_bitmap, torch::Tensor buf, torch::Tensor topics_off,
                          torch::Tensor topics_cnt, torch::Tensor disc) {
-    CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap);
-    TORCH_CHECK(sub_bitmap.dim() == 2 && sub_bitmap.size(0) == 256);
-    return k2a_mask(sub_bitmap, buf, disc, false, [&](uint64_t* mask, int32_t M, int32_t W) {
-        launch_k2a_topic_mask((const uint64_t*)sub_bitmap.data_ptr<int64_t>(),
-                              buf.data_ptr<uint8_t>(), topics_off.data_ptr<int64_t>(),
-                              topics_cnt.data_ptr<int32_t>(), disc.data_ptr<int32_t>(), mask, M,
-                              W, cur_stream());
-    });
+    Op a("topic_mask");
+    const TopicArgs t = topic_args(a, sub_bitmap, buf, topics_off, topics_cnt, disc);
+    hipStream_t s = a.begin();
+    auto mask = torch::empty({t.M, t.W}, opts(torch::kInt64, buf));
+    if (t.M > 0) {
+        launch_k2a_topic_mask(t.sub_bitmap, t.buf, t.topics_off, t.topics_cnt, t.disc,
+                              a.ptr<uint64_t>(mask, "mask"), t.M, t.W, s);
+        a.launched();
+    }
+    return mask;
 }
 
 std::vector<torch::Tensor> assign_emit(torch::Tensor mask, torch::Tensor payload_off,
                                        torch::Tensor payload_len, torch::Tensor ring_wpos,
                                        int64_t ring_bytes, int64_t n_users) {
-    CHECK_DEV(mask); CHECK_CONTIG(mask);
-    int32_t M = (int32_t)mask.size(0);
-    int32_t W = (int32_t)mask.size(1);
-    TORCH_CHECK(ring_bytes % 16 == 0, "ring_bytes must be a multiple of 16");
+    Op a("assign_emit");
+    const uint64_t* mk = a.ptr<uint64_t>(mask, "mask", 0, mat());
+    const int32_t M = a.i32(mask.size(0), "M");
+    const int32_t W = a.i32(mask.size(1), "W");
+    // n = 0 would read cum[-1] below
+    const int32_t n = a.i32(n_users, "n_users", 1, int64_t(W) * 64);
+    a.ring_bytes(ring_bytes);
+    const int64_t* poff = a.ptr<int64_t>(payload_off, "payload_off", M);
+    const int32_t* plen = a.ptr<int32_t>(payload_len, "payload_len", M);
+    uint64_t* wpos = a.ptr<uint64_t>(ring_wpos, "ring_wpos", n);
+    hipStream_t s = a.begin();
     auto o32 = opts(torch::kInt32, mask);
-    auto counts = torch::zeros({n_users}, o32);
-    launch_k2b_count((const uint64_t*)mask.data_ptr<int64_t>(), M, W, (int32_t)n_users,
-                     counts.data_ptr<int32_t>(), cur_stream());
+    auto counts = torch::zeros({n}, o32);
+    launch_k2b_count(mk, M, W, n, a.ptr<int32_t>(counts, "counts"), s);
+    a.launched();
     auto cum = counts.cumsum(0).to(torch::kInt32);
     auto pair_base = (cum - counts).contiguous();  // exclusive scan
-    int64_t total = cum[n_users - 1].item<int32_t>();  // one small D2H sync
+    int64_t total = cum[n - 1].item<int32_t>();  // one small D2H sync
     auto pairs = torch::empty({total, 4}, o32);
     auto drops = torch::zeros({1}, o32);
-    launch_k2b_emit((const uint64_t*)mask.data_ptr<int64_t>(), payload_off.data_ptr<int64_t>(),
-                    payload_len.data_ptr<int32_t>(), pair_base.data_ptr<int32_t>(), M, W,
-                    (int32_t)n_users, ring_bytes, (uint64_t*)ring_wpos.data_ptr<int64_t>(),
-                    pair_ptr(pairs), (uint32_t*)drops.data_ptr<int32_t>(), cur_stream());
+    launch_k2b_emit(mk, poff, plen, a.ptr<int32_t>(pair_base, "pair_base"), M, W, n, ring_bytes,
+                    wpos, a.pairs(pairs), a.ptr<uint32_t>(drops, "drops"), s);
+    a.launched();
     // split the AoS records back into the golden-test API's three tensors
     auto pair_user = pairs.select(1, 0).contiguous();
     auto pair_msg = pairs.select(1, 1).contiguous();
@@ -125,97 +252,139 @@ std::vector<torch::Tensor> assign_emit(torch::Tensor mask, torch::Tensor payload
 void fanout(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor payload_len,
             torch::Tensor pair_user, torch::Tensor pair_msg, torch::Tensor pair_dst,
             torch::Tensor msg_seq, torch::Tensor egress) {
-    CHECK_DEV(egress); CHECK_CONTIG(egress);
-    int32_t n_pairs = (int32_t)pair_user.size(0);
+    Op a("fanout");
+    const uint8_t* b = a.ptr<uint8_t>(buf, "buf");
+    const int64_t L = payload_off.numel();
+    const int64_t* poff = a.ptr<int64_t>(payload_off, "payload_off");
+    const int32_t* plen = a.same<int32_t>(payload_len, "payload_len", L, "one per payload_off");
+    const int32_t n_pairs = a.i32(pair_user.numel(), "pair count");
+    a.ptr<int32_t>(pair_user, "pair_user");
+    a.same<int32_t>(pair_msg, "pair_msg", n_pairs, "one per pair_user");
+    a.same<int64_t>(pair_dst, "pair_dst", n_pairs, "one per pair_user");
+    const uint32_t* seq = a.same<uint32_t>(msg_seq, "msg_seq", L, "one per payload_off");
+    uint8_t* eg = a.ptr<uint8_t>(egress, "egress");
+    hipStream_t s = a.begin();
     if (n_pairs == 0) return;
     auto pairs = torch::empty({n_pairs, 4}, opts(torch::kInt32, buf));
     pairs.select(1, 0).copy_(pair_user);
     pairs.select(1, 1).copy_(pair_msg);
     pairs.slice(1, 2, 4).view(torch::kInt64).squeeze(1).copy_(pair_dst);
-    launch_k3_fanout(buf.data_ptr<uint8_t>(), payload_off.data_ptr<int64_t>(),
-                     payload_len.data_ptr<int32_t>(), pair_ptr(pairs),
-                     (const uint32_t*)msg_seq.data_ptr<int32_t>(), n_pairs,
-                     egress.data_ptr<uint8_t>(), cur_stream());
+    launch_k3_fanout(b, poff, plen, a.pairs(pairs), seq, n_pairs, eg, s);
+    a.launched();
 }
 
 torch::Tensor direct_lookup(torch::Tensor table_keys, torch::Tensor table_vals,
                             torch::Tensor query) {
-    CHECK_DEV(table_keys); CHECK_DEV(query);
-    int64_t S = table_keys.size(0);
-    TORCH_CHECK((S & (S - 1)) == 0, "table size must be a power of two");
-    int32_t N = (int32_t)query.size(0);
+    Op a("direct_lookup");
+    const uint64_t* keys = a.ptr<uint64_t>(table_keys, "table_keys", 1, vec());
+    const int64_t S = table_keys.numel();
+    TORCH_CHECK((S & (S - 1)) == 0, a.name(), ": table_keys must have a power-of-two length, got ",
+                S);
+    const int32_t* vals = a.same<int32_t>(table_vals, "table_vals", S, "one per table_keys", vec());
+    const uint64_t* q = a.ptr<uint64_t>(query, "query");
+    const int32_t N = a.i32(query.numel(), "N");
+    hipStream_t s = a.begin();
     auto owner = torch::empty({N}, opts(torch::kInt32, query));
     if (N > 0) {
-        launch_k5_direct_lookup((const uint64_t*)table_keys.data_ptr<int64_t>(),
-                                table_vals.data_ptr<int32_t>(), S,
-                                (const uint64_t*)query.data_ptr<int64_t>(), N,
-                                owner.data_ptr<int32_t>(), cur_stream());
+        launch_k5_direct_lookup(keys, vals, S, q, N, a.ptr<int32_t>(owner, "owner"), s);
+        a.launched();
     }
     return owner;
 }
 
 void apply_subs(torch::Tensor sub_bitmap, torch::Tensor buf, torch::Tensor topics_off,
                 torch::Tensor topics_cnt, torch::Tensor disc, torch::Tensor user_idx) {
-    CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap);
-    int32_t W = (int32_t)sub_bitmap.size(1);
-    int32_t M = (int32_t)disc.size(0);
-    if (M == 0) return;
-    launch_k2c_apply_subs((uint64_t*)sub_bitmap.data_ptr<int64_t>(), buf.data_ptr<uint8_t>(),
-                          topics_off.data_ptr<int64_t>(), topics_cnt.data_ptr<int32_t>(),
-                          disc.data_ptr<int32_t>(), user_idx.data_ptr<int32_t>(), M, W,
-                          cur_stream());
+    Op a("apply_subs");
+    const TopicArgs t = topic_args(a, sub_bitmap, buf, topics_off, topics_cnt, disc);
+    const int32_t* uidx = a.same<int32_t>(user_idx, "user_idx", t.M, "one per disc");
+    hipStream_t s = a.begin();
+    if (t.M == 0) return;
+    launch_k2c_apply_subs(t.sub_bitmap, t.buf, t.topics_off, t.topics_cnt, t.disc, uidx, t.M,
+                          t.W, s);
+    a.launched();
+}
+
+// What the K1 ops share: N items = moff's length - 1, vks [N][128], sigs
+// [N][64], the flat messages; g2_lines and rand_r where the op takes them.
+// An op that takes no vks / sigs / g2_lines / rand_r passes nullptr.
+struct K1Args {
+    const uint8_t* vks = nullptr;
+    const uint8_t* sigs = nullptr;
+    uint8_t* msgs;
+    const int64_t* moff;
+    const uint8_t* g2_lines = nullptr;
+    const uint64_t* rand_r = nullptr;
+    int32_t N;
+};
+
+static K1Args k1_args(Op& a, const torch::Tensor* vks, const torch::Tensor* sigs,
+                      const torch::Tensor& msgs, const torch::Tensor& moff,
+                      const torch::Tensor* g2_lines = nullptr,
+                      const torch::Tensor* rand_r = nullptr) {
+    K1Args k;
+    const int64_t N = moff.numel() - 1;
+    if (vks) k.vks = a.same<uint8_t>(*vks, "vks", N * 128, "128 per interval of moff");
+    if (sigs) k.sigs = a.same<uint8_t>(*sigs, "sigs", N * 64, "64 per interval of moff");
+    k.msgs = a.ptr<uint8_t>(msgs, "msgs");
+    k.moff = a.ptr<int64_t>(moff, "moff", 1, vec());
+    if (g2_lines) k.g2_lines = a.ptr<uint8_t>(*g2_lines, "g2_lines", 128 * 192);
+    if (rand_r) k.rand_r = a.ptr<uint64_t>(*rand_r, "rand_r", N);
+    k.N = a.i32(N, "N");
+    return k;
 }
 
 torch::Tensor bls_verify_batch(torch::Tensor vks, torch::Tensor sigs, torch::Tensor msgs,
                                torch::Tensor moff) {
-    CHECK_DEV(vks); CHECK_DEV(sigs); CHECK_DEV(msgs); CHECK_DEV(moff);
-    CHECK_CONTIG(vks); CHECK_CONTIG(sigs); CHECK_CONTIG(msgs); CHECK_CONTIG(moff);
-    int32_t N = (int32_t)moff.size(0) - 1;
-    TORCH_CHECK(vks.numel() == (int64_t)N * 128 && sigs.numel() == (int64_t)N * 64);
-    auto ok = torch::zeros({N}, opts(torch::kInt32, vks));
-    if (N > 0) {
-        launch_k1_bls_verify(vks.data_ptr<uint8_t>(), sigs.data_ptr<uint8_t>(),
-                             msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(), N,
-                             ok.data_ptr<int32_t>(), cur_stream());
+    Op a("bls_verify_batch");
+    const K1Args k = k1_args(a, &vks, &sigs, msgs, moff);
+    hipStream_t s = a.begin();
+    auto ok = torch::zeros({k.N}, opts(torch::kInt32, vks));
+    if (k.N > 0) {
+        launch_k1_bls_verify(k.vks, k.sigs, k.msgs, k.moff, k.N, a.ptr<int32_t>(ok, "ok"), s);
+        a.launched();
     }
     return ok;
 }
 
 void compact_rings(torch::Tensor egress, int64_t ring_bytes, torch::Tensor wpos,
                    torch::Tensor dst_off, torch::Tensor staging, int64_t max_chunks) {
-    CHECK_DEV(egress); CHECK_DEV(wpos); CHECK_DEV(dst_off); CHECK_DEV(staging);
-    CHECK_CONTIG(egress); CHECK_CONTIG(wpos); CHECK_CONTIG(dst_off); CHECK_CONTIG(staging);
-    TORCH_CHECK(wpos.dtype() == torch::kInt64 && dst_off.dtype() == torch::kInt64);
-    int32_t n = (int32_t)wpos.size(0);
-    launch_k7_compact_rings(egress.data_ptr<uint8_t>(), ring_bytes,
-                            wpos.data_ptr<int64_t>(), dst_off.data_ptr<int64_t>(),
-                            staging.data_ptr<uint8_t>(), n, (int32_t)max_chunks,
-                            cur_stream());
+    Op a("compact_rings");
+    const int32_t n = a.i32(wpos.numel(), "ring count");
+    const int32_t chunks = a.i32(max_chunks, "max_chunks");
+    TORCH_CHECK(ring_bytes >= 0, a.name(), ": ring_bytes = ", ring_bytes, " is negative");
+    const uint8_t* eg = a.ptr<uint8_t>(egress, "egress", n * ring_bytes);
+    const int64_t* wp = a.ptr<int64_t>(wpos, "wpos", 0, vec());
+    const int64_t* doff = a.ptr<int64_t>(dst_off, "dst_off", n);
+    uint8_t* st = a.ptr<uint8_t>(staging, "staging");
+    hipStream_t s = a.begin();
+    if (n == 0 || chunks == 0) return;
+    launch_k7_compact_rings(eg, ring_bytes, wp, doff, st, n, chunks, s);
+    a.launched();
 }
 
 torch::Tensor precompute_g2_lines(torch::Tensor device_probe) {
     // fixed-g2 Miller-loop line coefficients (128 records x 192 B); computed
     // once per process by a 1-thread kernel, consumed by bls_verify_batch2
+    Op a("precompute_g2_lines");
+    a.ptr<uint8_t>(device_probe, "device_probe");
+    hipStream_t s = a.begin();
     auto out = torch::zeros({128 * 192}, opts(torch::kUInt8, device_probe));
     auto n = torch::zeros({1}, opts(torch::kInt32, device_probe));
-    launch_k1_precompute_g2_lines(out.data_ptr<uint8_t>(), n.data_ptr<int32_t>(),
-                                  cur_stream());
+    launch_k1_precompute_g2_lines(a.ptr<uint8_t>(out, "out"), a.ptr<int32_t>(n, "n"), s);
+    a.launched();
     return out;
 }
 
 torch::Tensor bls_verify_batch2(torch::Tensor vks, torch::Tensor sigs, torch::Tensor msgs,
                                 torch::Tensor moff, torch::Tensor g2_lines) {
-    CHECK_DEV(vks); CHECK_DEV(sigs); CHECK_DEV(msgs); CHECK_DEV(moff); CHECK_DEV(g2_lines);
-    CHECK_CONTIG(vks); CHECK_CONTIG(sigs); CHECK_CONTIG(msgs); CHECK_CONTIG(moff);
-    CHECK_CONTIG(g2_lines);
-    int32_t N = (int32_t)moff.size(0) - 1;
-    TORCH_CHECK(vks.numel() == (int64_t)N * 128 && sigs.numel() == (int64_t)N * 64);
-    auto ok = torch::zeros({N}, opts(torch::kInt32, vks));
-    if (N > 0) {
-        launch_k1_bls_verify2(vks.data_ptr<uint8_t>(), sigs.data_ptr<uint8_t>(),
-                              msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(),
-                              g2_lines.data_ptr<uint8_t>(), N, ok.data_ptr<int32_t>(),
-                              cur_stream());
+    Op a("bls_verify_batch2");
+    const K1Args k = k1_args(a, &vks, &sigs, msgs, moff, &g2_lines);
+    hipStream_t s = a.begin();
+    auto ok = torch::zeros({k.N}, opts(torch::kInt32, vks));
+    if (k.N > 0) {
+        launch_k1_bls_verify2(k.vks, k.sigs, k.msgs, k.moff, k.g2_lines, k.N,
+                              a.ptr<int32_t>(ok, "ok"), s);
+        a.launched();
     }
     return ok;
 }
@@ -223,127 +392,199 @@ torch::Tensor bls_verify_batch2(torch::Tensor vks, torch::Tensor sigs, torch::Te
 torch::Tensor bls_verify_batch_wave(torch::Tensor vks, torch::Tensor sigs,
                                     torch::Tensor msgs, torch::Tensor moff,
                                     torch::Tensor g2_lines, torch::Tensor rand_r) {
-    CHECK_DEV(vks); CHECK_DEV(sigs); CHECK_DEV(msgs); CHECK_DEV(moff); CHECK_DEV(g2_lines);
-    CHECK_DEV(rand_r);
-    CHECK_CONTIG(vks); CHECK_CONTIG(sigs); CHECK_CONTIG(msgs); CHECK_CONTIG(moff);
-    CHECK_CONTIG(g2_lines); CHECK_CONTIG(rand_r);
-    int32_t N = (int32_t)moff.size(0) - 1;
-    TORCH_CHECK(vks.numel() == (int64_t)N * 128 && sigs.numel() == (int64_t)N * 64);
-    TORCH_CHECK(rand_r.numel() >= N && rand_r.dtype() == torch::kInt64);
-    auto ok = torch::zeros({N}, opts(torch::kInt32, vks));
-    if (N > 0) {
-        launch_k1_bls_verify_wave(vks.data_ptr<uint8_t>(), sigs.data_ptr<uint8_t>(),
-                                  msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(),
-                                  g2_lines.data_ptr<uint8_t>(),
-                                  (const uint64_t*)rand_r.data_ptr<int64_t>(), N,
-                                  ok.data_ptr<int32_t>(), cur_stream());
+    Op a("bls_verify_batch_wave");
+    const K1Args k = k1_args(a, &vks, &sigs, msgs, moff, &g2_lines, &rand_r);
+    hipStream_t s = a.begin();
+    auto ok = torch::zeros({k.N}, opts(torch::kInt32, vks));
+    if (k.N > 0) {
+        launch_k1_bls_verify_wave(k.vks, k.sigs, k.msgs, k.moff, k.g2_lines, k.rand_r, k.N,
+                                  a.ptr<int32_t>(ok, "ok"), s);
+        a.launched();
     }
     return ok;
 }
 
 torch::Tensor hash_to_g1_batch(torch::Tensor msgs, torch::Tensor moff) {
-    CHECK_DEV(msgs); CHECK_DEV(moff);
-    int32_t N = (int32_t)moff.size(0) - 1;
-    auto out = torch::zeros({N, 64}, opts(torch::kUInt8, msgs));
-    if (N > 0) {
-        launch_k1_hash_to_g1(msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(), N,
-                             out.data_ptr<uint8_t>(), cur_stream());
+    Op a("hash_to_g1_batch");
+    const K1Args k = k1_args(a, nullptr, nullptr, msgs, moff);
+    hipStream_t s = a.begin();
+    auto out = torch::zeros({k.N, 64}, opts(torch::kUInt8, msgs));
+    if (k.N > 0) {
+        launch_k1_hash_to_g1(k.msgs, k.moff, k.N, a.ptr<uint8_t>(out, "out"), s);
+        a.launched();
     }
     return out;
+}
+
+// What the pair-list fan-outs share: the batch, the per-message offset and
+// length columns (one length), the pair list with its device-side count,
+// and the egress rings.
+struct FanoutArgs {
+    const uint8_t* buf;
+    const int64_t* payload_off;
+    const int32_t* payload_len;
+    const PairRec* pairs;
+    const int32_t* n_pairs;
+    uint8_t* egress;
+    int32_t capacity;
+    int nt, grid;    // nt is a flag
+    int64_t n_msgs;  // the columns' length, for a msg_seq column to match
+};
+
+static FanoutArgs fanout_args(Op& a, const torch::Tensor& buf, const torch::Tensor& payload_off,
+                              const torch::Tensor& payload_len, const torch::Tensor& pairs,
+                              const torch::Tensor& n_pairs, const torch::Tensor& egress,
+                              int64_t nt, int64_t grid) {
+    FanoutArgs f;
+    f.buf = a.ptr<uint8_t>(buf, "buf");
+    f.n_msgs = payload_off.numel();
+    f.payload_off = a.ptr<int64_t>(payload_off, "payload_off");
+    f.payload_len = a.same<int32_t>(payload_len, "payload_len", f.n_msgs, "one per payload_off");
+    f.pairs = a.pairs(pairs);
+    f.capacity = a.i32(pairs.size(0), "pair capacity");
+    f.n_pairs = a.ptr<int32_t>(n_pairs, "n_pairs", 1);
+    f.egress = a.ptr<uint8_t>(egress, "egress");
+    f.nt = nt != 0;
+    f.grid = a.i32(grid, "grid");
+    return f;
 }
 
 void fanout_wave(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor payload_len,
                  torch::Tensor pairs,
                  torch::Tensor msg_seq, torch::Tensor n_pairs, torch::Tensor egress,
                  int64_t nt, int64_t grid) {
-    CHECK_DEV(egress); CHECK_CONTIG(egress);
-    launch_k3_fanout_wave(buf.data_ptr<uint8_t>(), payload_off.data_ptr<int64_t>(),
-                          payload_len.data_ptr<int32_t>(), pair_ptr(pairs),
-                          (const uint32_t*)msg_seq.data_ptr<int32_t>(),
-                          n_pairs.data_ptr<int32_t>(), (int32_t)pairs.size(0),
-                          egress.data_ptr<uint8_t>(), (int)nt,
-                          (int)grid, cur_stream());
+    Op a("fanout_wave");
+    const FanoutArgs f = fanout_args(a, buf, payload_off, payload_len, pairs, n_pairs, egress,
+                                     nt, grid);
+    const uint32_t* seq = a.same<uint32_t>(msg_seq, "msg_seq", f.n_msgs, "one per payload_off");
+    hipStream_t s = a.begin();
+    launch_k3_fanout_wave(f.buf, f.payload_off, f.payload_len, f.pairs, seq, f.n_pairs,
+                          f.capacity, f.egress, f.nt, f.grid, s);
+    a.launched();
 }
 
 void fanout_ref(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor payload_len,
                 torch::Tensor pairs,
                 torch::Tensor msg_seq, torch::Tensor n_pairs, torch::Tensor egress,
                 int64_t nt, int64_t grid, int64_t ref_threshold, int64_t ref_base) {
-    CHECK_DEV(egress); CHECK_CONTIG(egress);
-    TORCH_CHECK(ref_threshold >= 0 && ref_threshold <= INT32_MAX,
-                "ref_threshold must fit an int32 length");
-    TORCH_CHECK(ref_base >= 0, "ref_base must not be negative");
-    launch_k3_fanout_ref(buf.data_ptr<uint8_t>(), payload_off.data_ptr<int64_t>(),
-                         payload_len.data_ptr<int32_t>(), pair_ptr(pairs),
-                         (const uint32_t*)msg_seq.data_ptr<int32_t>(),
-                         n_pairs.data_ptr<int32_t>(), (int32_t)pairs.size(0),
-                         (int32_t)ref_threshold, ref_base,
-                         egress.data_ptr<uint8_t>(), (int)nt,
-                         (int)grid, cur_stream());
+    Op a("fanout_ref");
+    const FanoutArgs f = fanout_args(a, buf, payload_off, payload_len, pairs, n_pairs, egress,
+                                     nt, grid);
+    const uint32_t* seq = a.same<uint32_t>(msg_seq, "msg_seq", f.n_msgs, "one per payload_off");
+    const int32_t thr = a.i32(ref_threshold, "ref_threshold");
+    TORCH_CHECK(ref_base >= 0, a.name(), ": ref_base = ", ref_base, " must not be negative");
+    hipStream_t s = a.begin();
+    launch_k3_fanout_ref(f.buf, f.payload_off, f.payload_len, f.pairs, seq, f.n_pairs,
+                         f.capacity, thr, ref_base, f.egress, f.nt, f.grid, s);
+    a.launched();
+}
+
+// fanout_flat2 (seq_state == nullptr: the seq base comes by value, mod 2^32)
+// and fanout_flat3 (the seq base is read from the device counter seq_state).
+static void fanout_flat(const char* op, const torch::Tensor& buf,
+                        const torch::Tensor& payload_off, const torch::Tensor& payload_len,
+                        const torch::Tensor& pairs, int64_t seq_base,
+                        const torch::Tensor* seq_state, const torch::Tensor& n_pairs,
+                        int64_t units_per_pair, const torch::Tensor& egress, int64_t nt,
+                        int64_t grid, int64_t uniform_len) {
+    Op a(op);
+    const FanoutArgs f = fanout_args(a, buf, payload_off, payload_len, pairs, n_pairs, egress,
+                                     nt, grid);
+    const uint32_t* state = seq_state ? a.ptr<uint32_t>(*seq_state, "seq_state", 1) : nullptr;
+    check_flat_shape(pairs, units_per_pair);
+    const int32_t units = a.i32(units_per_pair, "units_per_pair");
+    const int32_t ulen = a.i32(uniform_len, "uniform_len");
+    hipStream_t s = a.begin();
+    if (state)
+        launch_k3_fanout_flat3(f.buf, f.payload_off, f.payload_len, f.pairs, state, f.n_pairs,
+                               f.capacity, units, ulen, f.egress, f.nt, f.grid, s);
+    else
+        launch_k3_fanout_flat2(f.buf, f.payload_off, f.payload_len, f.pairs, (uint32_t)seq_base,
+                               f.n_pairs, f.capacity, units, ulen, f.egress, f.nt, f.grid, s);
+    a.launched();
 }
 
 void fanout_flat2(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor payload_len,
                   torch::Tensor pairs,
                   int64_t seq_base, torch::Tensor n_pairs, int64_t units_per_pair,
                   torch::Tensor egress, int64_t nt, int64_t grid, int64_t uniform_len) {
-    CHECK_DEV(egress); CHECK_CONTIG(egress);
-    pair_ptr(pairs);
-    check_flat_shape(pairs, units_per_pair);
-    int32_t capacity = (int32_t)pairs.size(0);
-    launch_k3_fanout_flat2(buf.data_ptr<uint8_t>(), payload_off.data_ptr<int64_t>(),
-                           payload_len.data_ptr<int32_t>(), pair_ptr(pairs),
-                           (uint32_t)seq_base, n_pairs.data_ptr<int32_t>(), capacity,
-                           (int32_t)units_per_pair, (int32_t)uniform_len,
-                           egress.data_ptr<uint8_t>(), (int)nt, (int)grid, cur_stream());
+    fanout_flat("fanout_flat2", buf, payload_off, payload_len, pairs, seq_base, nullptr, n_pairs,
+                units_per_pair, egress, nt, grid, uniform_len);
 }
 
 void fanout_flat3(torch::Tensor buf, torch::Tensor payload_off, torch::Tensor payload_len,
                   torch::Tensor pairs,
                   torch::Tensor seq_state, torch::Tensor n_pairs, int64_t units_per_pair,
                   torch::Tensor egress, int64_t nt, int64_t grid, int64_t uniform_len) {
-    CHECK_DEV(egress); CHECK_CONTIG(egress);
-    pair_ptr(pairs);
-    check_flat_shape(pairs, units_per_pair);
-    int32_t capacity = (int32_t)pairs.size(0);
-    launch_k3_fanout_flat3(buf.data_ptr<uint8_t>(), payload_off.data_ptr<int64_t>(),
-                           payload_len.data_ptr<int32_t>(), pair_ptr(pairs),
-                           (const uint32_t*)seq_state.data_ptr<int32_t>(),
-                           n_pairs.data_ptr<int32_t>(), capacity, (int32_t)units_per_pair,
-                           (int32_t)uniform_len, egress.data_ptr<uint8_t>(), (int)nt,
-                           (int)grid, cur_stream());
+    fanout_flat("fanout_flat3", buf, payload_off, payload_len, pairs, 0, &seq_state, n_pairs,
+                units_per_pair, egress, nt, grid, uniform_len);
 }
 
 void seq_advance(torch::Tensor seq_state, int64_t m) {
-    launch_k_seq_advance((uint32_t*)seq_state.data_ptr<int32_t>(), (int32_t)m, cur_stream());
+    Op a("seq_advance");
+    uint32_t* state = a.ptr<uint32_t>(seq_state, "seq_state", 1);
+    const int32_t m32 = a.i32(m, "m");
+    launch_k_seq_advance(state, m32, a.begin());
+    a.launched();
 }
 
 torch::Tensor topic_mask_t(torch::Tensor sub_bitmap, torch::Tensor buf,
                            torch::Tensor topics_off, torch::Tensor topics_cnt,
                            torch::Tensor disc) {
-    CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap);
-    return k2a_mask(sub_bitmap, buf, disc, true, [&](uint64_t* mask_t, int32_t M, int32_t W) {
-        launch_k2a_topic_mask_t((const uint64_t*)sub_bitmap.data_ptr<int64_t>(),
-                                buf.data_ptr<uint8_t>(), topics_off.data_ptr<int64_t>(),
-                                topics_cnt.data_ptr<int32_t>(), disc.data_ptr<int32_t>(),
-                                mask_t, M, W, cur_stream());
-    });
+    Op a("topic_mask_t");
+    const TopicArgs t = topic_args(a, sub_bitmap, buf, topics_off, topics_cnt, disc);
+    hipStream_t s = a.begin();
+    auto mask_t = torch::empty({t.W, t.M}, opts(torch::kInt64, buf));
+    if (t.M > 0) {
+        launch_k2a_topic_mask_t(t.sub_bitmap, t.buf, t.topics_off, t.topics_cnt, t.disc,
+                                a.ptr<uint64_t>(mask_t, "mask_t"), t.M, t.W, s);
+        a.launched();
+    }
+    return mask_t;
+}
+
+// What the two transposed K2b ops share: mask_t [W][M], the recipient count
+// n within the mask's 64 W bits, one cursor per recipient, the pair list and
+// its two counters.
+struct EmitArgs {
+    const uint64_t* mask_t;
+    uint64_t* ring_wpos;
+    PairRec* pairs;
+    uint32_t* drops;
+    int32_t* n_pairs;
+    int32_t M, W, n, capacity;
+};
+
+static EmitArgs emit_args(Op& a, const torch::Tensor& mask_t, const torch::Tensor& ring_wpos,
+                          int64_t ring_bytes, int64_t n_users, const torch::Tensor& pairs,
+                          const torch::Tensor& drops, const torch::Tensor& n_pairs) {
+    EmitArgs e;
+    e.mask_t = a.ptr<uint64_t>(mask_t, "mask_t", 0, mat());
+    e.W = a.i32(mask_t.size(0), "W");
+    e.M = a.i32(mask_t.size(1), "M");
+    e.n = a.i32(n_users, "n_users", 0, int64_t(e.W) * 64);
+    a.ring_bytes(ring_bytes);
+    e.ring_wpos = a.ptr<uint64_t>(ring_wpos, "ring_wpos", e.n);
+    e.pairs = a.pairs(pairs);
+    e.capacity = a.i32(pairs.size(0), "pair capacity");
+    e.drops = a.ptr<uint32_t>(drops, "drops", 1);
+    e.n_pairs = a.ptr<int32_t>(n_pairs, "n_pairs", 1);
+    return e;
 }
 
 void assign_emit_fused_t(torch::Tensor mask_t, torch::Tensor payload_len,
                          torch::Tensor ring_wpos, int64_t ring_bytes, int64_t n_users,
                          torch::Tensor pairs, torch::Tensor drops, torch::Tensor n_pairs,
                          int64_t uniform_rec) {
-    CHECK_DEV(mask_t); CHECK_CONTIG(mask_t);
-    int32_t W = (int32_t)mask_t.size(0);
-    int32_t M = (int32_t)mask_t.size(1);
-    TORCH_CHECK(ring_bytes % 16 == 0);
-    int32_t capacity = (int32_t)pairs.size(0);
-    launch_k2b_fused_t((const uint64_t*)mask_t.data_ptr<int64_t>(),
-                       payload_len.data_ptr<int32_t>(), M, W, (int32_t)n_users, ring_bytes,
-                       capacity, (int32_t)uniform_rec,
-                       (uint64_t*)ring_wpos.data_ptr<int64_t>(),
-                       n_pairs.data_ptr<int32_t>(), pair_ptr(pairs),
-                       (uint32_t*)drops.data_ptr<int32_t>(), cur_stream());
+    Op a("assign_emit_fused_t");
+    const EmitArgs e = emit_args(a, mask_t, ring_wpos, ring_bytes, n_users, pairs, drops, n_pairs);
+    const int32_t* plen = a.ptr<int32_t>(payload_len, "payload_len", e.M);
+    const int32_t rec = a.i32(uniform_rec, "uniform_rec");
+    hipStream_t s = a.begin();
+    if (e.n == 0) return;  // no recipient: nothing to claim, and no grid to launch
+    launch_k2b_fused_t(e.mask_t, plen, e.M, e.W, e.n, ring_bytes, e.capacity, rec, e.ring_wpos,
+                       e.n_pairs, e.pairs, e.drops, s);
+    a.launched();
 }
 
 void assign_emit_blocks_t(torch::Tensor mask_t, torch::Tensor ring_wpos,
@@ -352,53 +593,78 @@ void assign_emit_blocks_t(torch::Tensor mask_t, torch::Tensor ring_wpos,
                           torch::Tensor ufit, torch::Tensor udst,
                           torch::Tensor pairs, torch::Tensor drops, torch::Tensor n_pairs,
                           int64_t uniform_rec) {
-    CHECK_DEV(mask_t); CHECK_CONTIG(mask_t);
-    int32_t W = (int32_t)mask_t.size(0);
-    int32_t M = (int32_t)mask_t.size(1);
-    TORCH_CHECK(ring_bytes % 16 == 0 && uniform_rec > 0);
-    int64_t NB = (M + 31) / 32;
-    TORCH_CHECK(bcount.numel() >= NB * W * 64 && pprefix.numel() >= NB * W * 64,
-                "k2b block scratch too small");
-    TORCH_CHECK(ubase.numel() >= W * 64 && ufit.numel() >= W * 64 && udst.numel() >= W * 64);
-    int32_t capacity = (int32_t)pairs.size(0);
-    launch_k2b_blocks_t((const uint64_t*)mask_t.data_ptr<int64_t>(), M, W, (int32_t)n_users,
-                        ring_bytes, capacity, (int32_t)uniform_rec,
-                        (uint64_t*)ring_wpos.data_ptr<int64_t>(),
-                        n_pairs.data_ptr<int32_t>(),
-                        bcount.data_ptr<int32_t>(), pprefix.data_ptr<int32_t>(),
-                        ubase.data_ptr<int32_t>(), ufit.data_ptr<int32_t>(),
-                        udst.data_ptr<int64_t>(),
-                        pair_ptr(pairs),
-                        (uint32_t*)drops.data_ptr<int32_t>(), cur_stream());
+    Op a("assign_emit_blocks_t");
+    const EmitArgs e = emit_args(a, mask_t, ring_wpos, ring_bytes, n_users, pairs, drops, n_pairs);
+    const int32_t rec = a.i32(uniform_rec, "uniform_rec", 1);
+    const int64_t W64 = int64_t(e.W) * 64, NB = k2b_blocks(e.M);
+    int32_t* bc = a.ptr<int32_t>(bcount, "bcount", NB * W64);
+    int32_t* pp = a.ptr<int32_t>(pprefix, "pprefix", NB * W64);
+    int32_t* ub = a.ptr<int32_t>(ubase, "ubase", W64);
+    int32_t* uf = a.ptr<int32_t>(ufit, "ufit", W64);
+    int64_t* ud = a.ptr<int64_t>(udst, "udst", W64);
+    hipStream_t s = a.begin();
+    if (e.n == 0) return;  // as in assign_emit_fused_t
+    launch_k2b_blocks_t(e.mask_t, e.M, e.W, e.n, ring_bytes, e.capacity, rec, e.ring_wpos,
+                        e.n_pairs, bc, pp, ub, uf, ud, e.pairs, e.drops, s);
+    a.launched();
+}
+
+// What the two K5b ops share: four per-message columns of disc's length M
+// (origin is a fifth where the op takes it), the cursors, the pair list and
+// its two counters.
+struct DirectArgs {
+    const int32_t* disc;
+    const int32_t* owner;
+    const int64_t* payload_off;
+    const int32_t* payload_len;
+    int32_t M, capacity;
+};
+
+static DirectArgs direct_args(Op& a, const torch::Tensor& disc, const torch::Tensor& owner,
+                              const torch::Tensor& payload_off, const torch::Tensor& payload_len,
+                              int64_t ring_bytes) {
+    DirectArgs d;
+    d.disc = a.ptr<int32_t>(disc, "disc");
+    d.M = a.i32(disc.numel(), "M");
+    d.owner = a.same<int32_t>(owner, "owner", d.M, "one per disc");
+    d.payload_off = a.same<int64_t>(payload_off, "payload_off", d.M, "one per disc");
+    d.payload_len = a.same<int32_t>(payload_len, "payload_len", d.M, "one per disc");
+    a.ring_bytes(ring_bytes);
+    return d;
 }
 
 void emit_direct(torch::Tensor disc, torch::Tensor owner, torch::Tensor payload_off,
                  torch::Tensor payload_len, int64_t ring_bytes, torch::Tensor ring_wpos,
                  torch::Tensor n_pairs, torch::Tensor pairs, torch::Tensor drops) {
-    int32_t M = (int32_t)disc.size(0);
-    if (M == 0) return;
-    int32_t capacity = (int32_t)pairs.size(0);
-    launch_k5b_emit_direct(disc.data_ptr<int32_t>(), owner.data_ptr<int32_t>(),
-                           payload_off.data_ptr<int64_t>(), payload_len.data_ptr<int32_t>(),
-                           M, ring_bytes, capacity, (uint64_t*)ring_wpos.data_ptr<int64_t>(),
-                           n_pairs.data_ptr<int32_t>(), pair_ptr(pairs),
-                           (uint32_t*)drops.data_ptr<int32_t>(), cur_stream());
+    Op a("emit_direct");
+    const DirectArgs d = direct_args(a, disc, owner, payload_off, payload_len, ring_bytes);
+    uint64_t* wpos = a.ptr<uint64_t>(ring_wpos, "ring_wpos");
+    int32_t* np = a.ptr<int32_t>(n_pairs, "n_pairs", 1);
+    PairRec* pr = a.pairs(pairs);
+    const int32_t capacity = a.i32(pairs.size(0), "pair capacity");
+    uint32_t* dr = a.ptr<uint32_t>(drops, "drops", 1);
+    hipStream_t s = a.begin();
+    if (d.M == 0) return;
+    launch_k5b_emit_direct(d.disc, d.owner, d.payload_off, d.payload_len, d.M, ring_bytes,
+                           capacity, wpos, np, pr, dr, s);
+    a.launched();
 }
 
 torch::Tensor topic_mask_origin_t(torch::Tensor sub_bitmap, torch::Tensor buf,
                                   torch::Tensor topics_off, torch::Tensor topics_cnt,
                                   torch::Tensor disc, torch::Tensor origin, int64_t n_users) {
-    CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap); CHECK_DEV(origin); CHECK_CONTIG(origin);
-    TORCH_CHECK(origin.dtype() == torch::kInt32 && origin.numel() == disc.size(0),
-                "origin must be an int32 [M] tensor");
-    TORCH_CHECK(n_users >= 0 && n_users <= sub_bitmap.size(1) * 64, "n_users outside the bitmap");
-    return k2a_mask(sub_bitmap, buf, disc, true, [&](uint64_t* mask_t, int32_t M, int32_t W) {
-        launch_k2a_topic_mask_origin_t(
-            (const uint64_t*)sub_bitmap.data_ptr<int64_t>(), buf.data_ptr<uint8_t>(),
-            topics_off.data_ptr<int64_t>(), topics_cnt.data_ptr<int32_t>(),
-            disc.data_ptr<int32_t>(), origin.data_ptr<int32_t>(), mask_t, M, W,
-            (int32_t)n_users, cur_stream());
-    });
+    Op a("topic_mask_origin_t");
+    const TopicArgs t = topic_args(a, sub_bitmap, buf, topics_off, topics_cnt, disc);
+    const int32_t* org = a.same<int32_t>(origin, "origin", t.M, "one per disc");
+    const int32_t n = a.i32(n_users, "n_users", 0, int64_t(t.W) * 64);
+    hipStream_t s = a.begin();
+    auto mask_t = torch::empty({t.W, t.M}, opts(torch::kInt64, buf));
+    if (t.M > 0) {
+        launch_k2a_topic_mask_origin_t(t.sub_bitmap, t.buf, t.topics_off, t.topics_cnt, t.disc,
+                                       org, a.ptr<uint64_t>(mask_t, "mask_t"), t.M, t.W, n, s);
+        a.launched();
+    }
+    return mask_t;
 }
 
 void emit_direct_peers(torch::Tensor disc, torch::Tensor owner, torch::Tensor origin,
@@ -406,43 +672,40 @@ void emit_direct_peers(torch::Tensor disc, torch::Tensor owner, torch::Tensor or
                        int64_t ring_bytes, int64_t n_users, int64_t n_peers,
                        torch::Tensor ring_wpos, torch::Tensor n_pairs, torch::Tensor pairs,
                        torch::Tensor drops) {
-    int32_t M = (int32_t)disc.size(0);
-    if (M == 0) return;
-    CHECK_DEV(origin); CHECK_CONTIG(origin); CHECK_DEV(ring_wpos); CHECK_CONTIG(ring_wpos);
-    TORCH_CHECK(origin.dtype() == torch::kInt32 && origin.numel() == M,
-                "origin must be an int32 [M] tensor");
-    TORCH_CHECK(owner.numel() == M && payload_len.numel() == M);
-    TORCH_CHECK(n_users >= 0 && n_peers >= 0 && ring_wpos.numel() >= n_users + n_peers,
-                "ring_wpos must cover n_users + n_peers rings");
-    int32_t capacity = (int32_t)pairs.size(0);
-    launch_k5b_emit_direct_peers(
-        disc.data_ptr<int32_t>(), owner.data_ptr<int32_t>(), origin.data_ptr<int32_t>(),
-        payload_off.data_ptr<int64_t>(), payload_len.data_ptr<int32_t>(), M,
-        (int32_t)n_users, (int32_t)n_peers, ring_bytes, capacity,
-        (uint64_t*)ring_wpos.data_ptr<int64_t>(), n_pairs.data_ptr<int32_t>(),
-        pair_ptr(pairs), (uint32_t*)drops.data_ptr<int32_t>(), cur_stream());
+    Op a("emit_direct_peers");
+    const DirectArgs d = direct_args(a, disc, owner, payload_off, payload_len, ring_bytes);
+    const int32_t* org = a.same<int32_t>(origin, "origin", d.M, "one per disc");
+    const int32_t n = a.i32(n_users, "n_users");
+    const int32_t p = a.i32(n_peers, "n_peers");
+    uint64_t* wpos = a.ptr<uint64_t>(ring_wpos, "ring_wpos", int64_t(n) + p);
+    int32_t* np = a.ptr<int32_t>(n_pairs, "n_pairs", 1);
+    PairRec* pr = a.pairs(pairs);
+    const int32_t capacity = a.i32(pairs.size(0), "pair capacity");
+    uint32_t* dr = a.ptr<uint32_t>(drops, "drops", 1);
+    hipStream_t s = a.begin();
+    if (d.M == 0) return;
+    launch_k5b_emit_direct_peers(d.disc, d.owner, org, d.payload_off, d.payload_len, d.M, n, p,
+                                 ring_bytes, capacity, wpos, np, pr, dr, s);
+    a.launched();
 }
 
 void direct_apply(torch::Tensor table_keys, torch::Tensor table_vals, torch::Tensor up_keys,
                   torch::Tensor up_owners, torch::Tensor del_keys, torch::Tensor n_failed) {
-    CHECK_DEV(table_keys); CHECK_DEV(table_vals); CHECK_DEV(up_keys); CHECK_DEV(up_owners);
-    CHECK_DEV(del_keys); CHECK_DEV(n_failed);
-    CHECK_CONTIG(table_keys); CHECK_CONTIG(table_vals); CHECK_CONTIG(up_keys);
-    CHECK_CONTIG(up_owners); CHECK_CONTIG(del_keys);
-    int64_t S = table_keys.size(0);
-    TORCH_CHECK(S > 0 && (S & (S - 1)) == 0, "table size must be a power of two");
-    TORCH_CHECK(table_vals.numel() == S && table_keys.dtype() == torch::kInt64
-                && table_vals.dtype() == torch::kInt32);
-    TORCH_CHECK(up_keys.dtype() == torch::kInt64 && del_keys.dtype() == torch::kInt64
-                && up_owners.dtype() == torch::kInt32 && n_failed.dtype() == torch::kInt32);
-    TORCH_CHECK(up_owners.numel() == up_keys.numel() && n_failed.numel() >= 1);
-    launch_k6_direct_apply((uint64_t*)table_keys.data_ptr<int64_t>(),
-                           table_vals.data_ptr<int32_t>(), S,
-                           (const uint64_t*)up_keys.data_ptr<int64_t>(),
-                           up_owners.data_ptr<int32_t>(), (int32_t)up_keys.numel(),
-                           (const uint64_t*)del_keys.data_ptr<int64_t>(),
-                           (int32_t)del_keys.numel(),
-                           (uint32_t*)n_failed.data_ptr<int32_t>(), cur_stream());
+    Op a("direct_apply");
+    uint64_t* keys = a.ptr<uint64_t>(table_keys, "table_keys", 1, vec());
+    const int64_t S = table_keys.numel();
+    TORCH_CHECK((S & (S - 1)) == 0, a.name(), ": table_keys must have a power-of-two length, got ",
+                S);
+    int32_t* vals = a.same<int32_t>(table_vals, "table_vals", S, "one per table_keys");
+    const uint64_t* up = a.ptr<uint64_t>(up_keys, "up_keys");
+    const int32_t n_up = a.i32(up_keys.numel(), "upsert count");
+    const int32_t* owners = a.same<int32_t>(up_owners, "up_owners", n_up, "one per up_keys");
+    const uint64_t* del = a.ptr<uint64_t>(del_keys, "del_keys");
+    const int32_t n_del = a.i32(del_keys.numel(), "delete count");
+    uint32_t* failed = a.ptr<uint32_t>(n_failed, "n_failed", 1);
+    hipStream_t s = a.begin();
+    launch_k6_direct_apply(keys, vals, S, up, owners, n_up, del, n_del, failed, s);
+    a.launched();
 }
 
 // The fused uniform broadcast tick (launch_tick_uniform_broadcast): one call
@@ -455,58 +718,47 @@ void tick_uniform_broadcast(torch::Tensor buf, torch::Tensor offsets, uint64_t h
                             torch::Tensor scratch64, torch::Tensor scratch32,
                             int64_t uniform_len, int64_t seq_base, torch::Tensor egress,
                             int64_t nt, int64_t dense) {
-    CHECK_DEV(buf); CHECK_CONTIG(buf); CHECK_DEV(offsets); CHECK_CONTIG(offsets);
-    CHECK_DEV(sub_bitmap); CHECK_CONTIG(sub_bitmap); CHECK_DEV(ring_wpos); CHECK_CONTIG(ring_wpos);
-    CHECK_DEV(egress); CHECK_CONTIG(egress); CHECK_DEV(scratch64); CHECK_DEV(scratch32);
-    CHECK_DEV(drops); CHECK_DEV(n_pairs); CHECK_DEV(n_sparse);
-    TORCH_CHECK(buf.dtype() == torch::kUInt8 && offsets.dtype() == torch::kInt64
-                && egress.dtype() == torch::kUInt8);
-    TORCH_CHECK(sub_bitmap.dim() == 2 && sub_bitmap.size(0) == 256);
-    const int64_t M = offsets.size(0) - 1, W = sub_bitmap.size(1);
-    if (M <= 0) return;
-    TORCH_CHECK(uniform_len >= 0 && uniform_len < (int64_t(1) << 30));
+    Op a("tick_uniform_broadcast");
+    UniformTick t;
+    t.uniform_len = a.i32(uniform_len, "uniform_len", 0, (int64_t(1) << 30) - 1);
     const int64_t rec = (uniform_len + 16 + 15) & ~int64_t(15);
-    TORCH_CHECK(ring_bytes % 16 == 0 && n_users >= 0 && n_users <= W * 64
-                && ring_wpos.numel() >= n_users && ring_wpos.dtype() == torch::kInt64
-                && egress.numel() >= n_users * ring_bytes,
-                "rings do not cover n_users");
-    TORCH_CHECK(buf.numel() >= M * uniform_len, "batch shorter than M uniform messages");
+    t.rec = a.i32(rec, "rec");
+    t.buf = a.ptr<uint8_t>(buf, "buf");
+    t.offsets = a.ptr<int64_t>(offsets, "offsets", 1);
+    const int64_t M = offsets.numel() - 1;
+    t.M = a.i32(M, "M");
+    t.hash_seed = hash_seed;
+    t.sub_bitmap = a.ptr<uint64_t>(sub_bitmap, "sub_bitmap", 0, mat(256, -1));
+    const int64_t W = sub_bitmap.size(1);
+    t.W = a.i32(W, "W");
+    t.n_users = a.i32(n_users, "n_users", 0, W * 64);
+    a.ring_bytes(ring_bytes);
+    t.ring_bytes = ring_bytes;
+    t.ring_wpos = a.ptr<uint64_t>(ring_wpos, "ring_wpos", n_users);
+    t.pairs = a.pairs(pairs);
+    t.capacity = a.i32(pairs.size(0), "pair capacity");
+    t.drops = a.ptr<uint32_t>(drops, "drops", 1);
+    t.n_pairs = a.ptr<int32_t>(n_pairs, "n_pairs", 1);
+    t.n_sparse = a.ptr<int32_t>(n_sparse, "n_sparse", 1);
+    t.scratch64 = a.ptr<int64_t>(scratch64, "scratch64", uniform_tick_scratch64(M, W, rec / 16));
+    t.scratch32 = a.ptr<int32_t>(scratch32, "scratch32", uniform_tick_scratch32(M, W));
+    t.egress = a.ptr<uint8_t>(egress, "egress", n_users * ring_bytes);
+    t.seq_base = (uint32_t)seq_base;  // sequence numbers count mod 2^32
+    t.nt = nt != 0;
+    t.dense = dense != 0;
+    TORCH_CHECK(buf.numel() >= M * uniform_len, a.name(), ": buf has ", buf.numel(),
+                " bytes, shorter than M = ", M, " messages of uniform_len = ", uniform_len);
     check_flat_shape(pairs, rec / 16);
     // the image kernel's unit index and the dense fan-out's 1-D grid
     TORCH_CHECK(M * (rec / 16) < (int64_t(1) << 31)
-                && dense_grid_x((int32_t)n_users, DENSE_GROUP, dense_geom((int32_t)(rec / 16)).n_chunks)
+                && dense_grid_x(t.n_users, DENSE_GROUP, dense_geom((int32_t)(rec / 16)).n_chunks)
                        * k2b_blocks(M) < (int64_t(1) << 31),
-                "batch too large for the dense fan-out");
-    TORCH_CHECK(scratch64.dtype() == torch::kInt64 && scratch32.dtype() == torch::kInt32
-                && scratch64.is_contiguous() && scratch32.is_contiguous()
-                && (uintptr_t)scratch64.data_ptr<int64_t>() % 16 == 0
-                && scratch64.numel() >= uniform_tick_scratch64(M, W, rec / 16)
-                && scratch32.numel() >= uniform_tick_scratch32(M, W),
-                "fused tick scratch too small");
-    UniformTick t;
-    t.buf = buf.data_ptr<uint8_t>();
-    t.offsets = offsets.data_ptr<int64_t>();
-    t.M = (int32_t)M;
-    t.hash_seed = hash_seed;
-    t.sub_bitmap = (const uint64_t*)sub_bitmap.data_ptr<int64_t>();
-    t.W = (int32_t)W;
-    t.n_users = (int32_t)n_users;
-    t.ring_bytes = ring_bytes;
-    t.capacity = (int32_t)pairs.size(0);
-    t.uniform_len = (int32_t)uniform_len;
-    t.rec = (int32_t)rec;
-    t.seq_base = (uint32_t)seq_base;
-    t.ring_wpos = (uint64_t*)ring_wpos.data_ptr<int64_t>();
-    t.n_pairs = n_pairs.data_ptr<int32_t>();
-    t.n_sparse = n_sparse.data_ptr<int32_t>();
-    t.pairs = pair_ptr(pairs);
-    t.drops = (uint32_t*)drops.data_ptr<int32_t>();
-    t.scratch64 = scratch64.data_ptr<int64_t>();
-    t.scratch32 = scratch32.data_ptr<int32_t>();
-    t.egress = egress.data_ptr<uint8_t>();
-    t.nt = (int)nt;
-    t.dense = (int)dense;
-    launch_tick_uniform_broadcast(&t, cur_stream());
+                a.name(), ": batch too large for the dense fan-out");
+    TORCH_CHECK((uintptr_t)t.scratch64 % 16 == 0, a.name(), ": scratch64 must be 16-byte aligned");
+    hipStream_t s = a.begin();
+    if (M == 0) return;
+    launch_tick_uniform_broadcast(&t, s);
+    a.launched();
 }
 
 std::vector<int64_t> uniform_tick_scratch_sizes(int64_t M, int64_t W, int64_t rec) {
@@ -517,22 +769,17 @@ std::vector<int64_t> uniform_tick_scratch_sizes(int64_t M, int64_t W, int64_t re
 // one async copy lands them in the engine's pinned `host` buffer, one stream
 // synchronise makes that buffer readable.
 void drain_cursors(torch::Tensor ring_wpos, torch::Tensor staging, torch::Tensor host) {
-    CHECK_DEV(ring_wpos); CHECK_CONTIG(ring_wpos); CHECK_DEV(staging); CHECK_CONTIG(staging);
-    TORCH_CHECK(!host.is_cuda() && host.is_pinned() && host.is_contiguous(),
-                "host must be a pinned CPU tensor");
-    TORCH_CHECK(ring_wpos.dtype() == torch::kInt64 && staging.dtype() == torch::kInt64
-                && host.dtype() == torch::kInt64);
-    const int64_t n = ring_wpos.numel();
-    TORCH_CHECK(staging.numel() >= n && host.numel() >= n && n <= INT32_MAX);
+    Op a("drain_cursors");
+    int64_t* wpos = a.ptr<int64_t>(ring_wpos, "ring_wpos");
+    const int32_t n = a.i32(ring_wpos.numel(), "cursor count");
+    int64_t* st = a.ptr<int64_t>(staging, "staging", n);
+    int64_t* h = a.ptr<int64_t>(host, "host", n, {}, Op::kPinnedHost);
+    hipStream_t s = a.begin();
     if (n == 0) return;
-    hipStream_t s = cur_stream();
-    launch_drain_cursors(ring_wpos.data_ptr<int64_t>(), staging.data_ptr<int64_t>(), (int32_t)n,
-                         s);
-    hipError_t e = hipMemcpyAsync(host.data_ptr<int64_t>(), staging.data_ptr<int64_t>(),
-                                  (size_t)n * 8, hipMemcpyDeviceToHost, s);
-    TORCH_CHECK(e == hipSuccess, "drain_cursors copy: ", hipGetErrorString(e));
-    e = hipStreamSynchronize(s);
-    TORCH_CHECK(e == hipSuccess, "drain_cursors sync: ", hipGetErrorString(e));
+    launch_drain_cursors(wpos, st, n, s);
+    a.launched();
+    a.check(hipMemcpyAsync(h, st, (size_t)n * 8, hipMemcpyDeviceToHost, s), "copy");
+    a.check(hipStreamSynchronize(s), "sync");
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -563,18 +810,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fixed-g2 Miller line coefficients for K1 v2 (once per process)");
     m.def("bls_verify_batch2", &bls_verify_batch2,
           "K1 v2: 2-lane Fp2-decomposed batched BLS verification");
-    m.def("_k1_dbg_wave",
-          [](torch::Tensor vks, torch::Tensor sigs, torch::Tensor msgs, torch::Tensor moff,
-             torch::Tensor g2_lines, torch::Tensor rand_r, int64_t mode) {
-              int32_t N = (int32_t)moff.size(0) - 1;
-              auto ok = torch::zeros({N}, opts(torch::kInt32, vks));
-              launch_k1_dbg_wave(vks.data_ptr<uint8_t>(), sigs.data_ptr<uint8_t>(),
-                                 msgs.data_ptr<uint8_t>(), moff.data_ptr<int64_t>(),
-                                 g2_lines.data_ptr<uint8_t>(),
-                                 (const uint64_t*)rand_r.data_ptr<int64_t>(), N,
-                                 (int32_t)mode, ok.data_ptr<int32_t>(), cur_stream());
-              return ok;
-          });
     m.def("bls_verify_batch_wave", &bls_verify_batch_wave,
           "K1 v3: wave-batched product verification (shared final exp, "
           "exact per-item fallback)");

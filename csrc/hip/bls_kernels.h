@@ -24,8 +24,5 @@ void launch_k1_bls_verify_wave(const uint8_t* vks, const uint8_t* sigs, uint8_t*
                                const int64_t* moff, const uint8_t* g2_lines,
                                const uint64_t* rand_r, int32_t N, int32_t* ok,
                                hipStream_t s);
-void launch_k1_dbg_wave(const uint8_t* vks, const uint8_t* sigs, uint8_t* msgs,
-                        const int64_t* moff, const uint8_t* g2_lines, const uint64_t* rand_r,
-                        int32_t N, int32_t mode, int32_t* ok, hipStream_t s);
 
 }  // extern "C"
