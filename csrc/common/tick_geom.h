@@ -1,7 +1,8 @@
 // Host-side geometry of the fused uniform broadcast tick
 // (launch_tick_uniform_broadcast, csrc/hip/dataplane.hip): block size, dense
-// fan-out chunking and scratch sizes.  Plain C++ with no HIP dependency, so
-// csrc/tests/test_native.cpp checks it on the CPU.
+// fan-out chunking, scratch sizes and the route kernel's LDS layout.  Plain
+// C++ with no HIP dependency, so csrc/tests/test_native.cpp checks it on the
+// CPU.
 #pragma once
 
 #include <stdint.h>
@@ -44,6 +45,9 @@ static inline int64_t dense_grid_x(int32_t n_users, int32_t group, int32_t n_chu
 //           mask_t [W][M], tdst [NB][U], udst [U]
 //   32-bit: disc, payload_len, topics_cnt [M] each, bcount, pprefix,
 //           tslot [NB][U] each, ulim, usbase [U] each
+// mask_t, udst and the 32-bit tile and user arrays are touched only by a
+// batch above ROUTE_MAX_M (below); the sizes and the carve order do not
+// depend on that.
 static inline int64_t k2b_blocks(int64_t M) { return (M + K2B_BLK - 1) / K2B_BLK; }
 static inline int64_t uniform_tick_scratch64(int64_t M, int64_t W, int64_t units_per_rec) {
     return 4 * M + W * M + k2b_blocks(M) * W * 64 + W * 64 + 2 * M * units_per_rec;
@@ -51,3 +55,40 @@ static inline int64_t uniform_tick_scratch64(int64_t M, int64_t W, int64_t units
 static inline int64_t uniform_tick_scratch32(int64_t M, int64_t W) {
     return 3 * M + 3 * k2b_blocks(M) * W * 64 + 2 * W * 64;
 }
+
+// The route kernel (k_route_word) runs K2a, P1, P2 and P3 for one mask word,
+// 64 users, in one workgroup and keeps what those kernels hand each other in
+// LDS.  Byte offsets of its arrays for a batch of M messages (NB blocks),
+// widest element first so each is aligned to its own type:
+//   mask    uint64 [M]        the word of every message's recipient mask
+//   udst    int64  [64]       ring address of the user's first record
+//   ulim    int32  [64]       records delivered at most
+//   usbase  int32  [64]       first sparse-list slot
+//   pprefix uint16 [NB][64]   deliveries before the block (<= M - 1)
+//   tslot   uint16 [NB][64]   sparse slot relative to usbase (<= M - 1)
+//   bcount  uint8  [NB][64]   set bits of the tile (<= K2B_BLK)
+// tdst is not here: the dense fan-out, a later launch, reads it from scratch.
+#define ROUTE_THREADS 256
+struct RouteLds { int32_t mask, udst, ulim, usbase, pprefix, tslot, bcount, bytes; };
+constexpr RouteLds route_lds(int32_t M) {
+    const int32_t tiles = (M + K2B_BLK - 1) / K2B_BLK * 64;
+    RouteLds l{};
+    l.mask = 0;
+    l.udst = l.mask + 8 * M;
+    l.ulim = l.udst + 8 * 64;
+    l.usbase = l.ulim + 4 * 64;
+    l.pprefix = l.usbase + 4 * 64;
+    l.tslot = l.pprefix + 2 * tiles;
+    l.bcount = l.tslot + 2 * tiles;
+    l.bytes = l.bcount + tiles;
+    return l;
+}
+// Largest batch the route kernel takes; a larger one runs the four kernels.
+// 18 bytes per message and 1 KiB per workgroup: 3,584 messages fill 64 KiB.
+#define ROUTE_MAX_M 3584
+static_assert(route_lds(ROUTE_MAX_M).bytes <= 64 * 1024, "route kernel LDS exceeds a workgroup's 64 KiB");
+static_assert(route_lds(ROUTE_MAX_M + 1).bytes > 64 * 1024, "ROUTE_MAX_M is not the largest batch that fits");
+static_assert(ROUTE_MAX_M >= 2048, "the 8-GPU bench routes 8 x 256 gathered messages per tick");
+static_assert(ROUTE_MAX_M <= 65535 && K2B_BLK <= 255, "prefixes are 16-bit, tile counts 8-bit");
+static_assert(route_lds(33).udst % 8 == 0 && route_lds(33).ulim % 4 == 0 && route_lds(33).pprefix % 2 == 0,
+              "route kernel LDS arrays are aligned to their element types");

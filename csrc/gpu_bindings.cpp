@@ -783,6 +783,8 @@ void drain_cursors(torch::Tensor ring_wpos, torch::Tensor staging, torch::Tensor
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    // largest batch tick_uniform_broadcast routes in one kernel (tick_geom.h)
+    m.attr("_ROUTE_MAX_M") = py::int_(ROUTE_MAX_M);
     m.def("tick_uniform_broadcast", &tick_uniform_broadcast,
           "fused uniform broadcast tick: K4, K2a, K2b tiles, dense + sparse fan-out");
     m.def("uniform_tick_scratch_sizes", &uniform_tick_scratch_sizes,

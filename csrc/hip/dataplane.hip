@@ -48,12 +48,16 @@
 //   K7  k7_compact_rings — gather used ring prefixes into one staging buffer
 //   fused uniform broadcast tick (launch_tick_uniform_broadcast, end of this
 //                        file) — the broadcast-only uniform shape as one
-//                        launcher call: K4, K2a, k2b_p1_count_z, k2b_p2_tiles
-//                        (P2 plus a dense / sparse sort of the (user, block)
-//                        tiles), k2b_p3_sparse (pairs for sparse tiles only),
-//                        k3d_image + k3_fanout_dense (dense tiles stored from
-//                        registers, no pair records) and the flat K3 over the
-//                        sparse list; k_drain_cursors is the fused drain
+//                        launcher call of four launches: k_tick_prologue (K4,
+//                        the dense fan-out's record image, counters zeroed),
+//                        k_route_word (K2a, P1, P2 plus a dense / sparse sort
+//                        of the (user, block) tiles, and pairs for the sparse
+//                        tiles only, one mask word per workgroup, in LDS),
+//                        k3_fanout_dense (dense tiles stored from registers,
+//                        no pair records) and the flat K3 over the sparse
+//                        list.  Above ROUTE_MAX_M messages k2a_topic_mask_t,
+//                        k2b_p1_count_z, k2b_p2_tiles and k2b_p3_sparse route
+//                        through scratch.  k_drain_cursors is the fused drain
 //
 // Shared device building blocks, each defined once and force-inlined:
 //   store16<NT>        the only place the non-temporal store choice is made
@@ -64,6 +68,11 @@
 //                      three K2a kernels
 //   wave_claim_span    wave64 inclusive scan + one atomicAdd per wave —
 //                      k2b_fused_t, k2b_p2_bases
+//   k4_parse_body      one message's parse — k4_parse_batch, k_tick_prologue
+//   k3d_image_body     one unit of the record image — k_tick_prologue
+//   k2b_tile_count, k2b_p2_body, k2b_tiles_body, k2b_p3_sparse_body
+//                      P1, P2, the tile sort and P3 over tiles in scratch or
+//                      in LDS — the k2b_p* kernels and k_route_word
 //   k5b_claim_emit     pair-slot claim, CAS ring claim, placeholder and drop
 //                      — both K5b kernels
 // The launcher prototypes and the PairRec / ParseOut structs are in
@@ -193,12 +202,13 @@ __device__ inline bool read_byte_list(const uint8_t* seg, int64_t nwords, int64_
     return true;
 }
 
-extern "C" __global__ void k4_parse_batch(
+// Message i of the batch; shared by k4_parse_batch and the fused tick's
+// prologue (k_tick_prologue).
+__device__ __forceinline__ void k4_parse_body(
     const uint8_t* __restrict__ buf,
     const int64_t* __restrict__ offsets,  // [M+1] byte offsets into buf
-    int32_t M, uint64_t hash_seed, ParseOut out)
+    int32_t M, uint64_t hash_seed, const ParseOut& out, int i)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
     // defaults; field values are buffered in locals and committed only
     // once the whole frame validates, so rejected records are all-zero
@@ -306,6 +316,14 @@ extern "C" __global__ void k4_parse_batch(
     out.topics_off[i] = o_toff;  out.topics_cnt[i] = o_tcnt;
     out.recip_hash[i] = (int64_t)o_rhash; out.timestamp[i] = o_ts;
     out.disc[i] = (int32_t)disc;
+}
+
+extern "C" __global__ void k4_parse_batch(
+    const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ offsets,  // [M+1] byte offsets into buf
+    int32_t M, uint64_t hash_seed, ParseOut out)
+{
+    k4_parse_body(buf, offsets, M, hash_seed, out, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -1032,6 +1050,8 @@ void launch_k2a_topic_mask_t(const uint64_t* sub_bitmap, const uint8_t* buf,
                        buf, topics_off, topics_cnt, disc, mask_t, M, W);
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------
 // K2b block-parallel variant for UNIFORM records.  The fused kernel above
 // runs one lane per user, so a 10k-user broker fills only ~157 wave slots
@@ -1047,6 +1067,23 @@ void launch_k2a_topic_mask_t(const uint64_t* sub_bitmap, const uint8_t* buf,
 // ---------------------------------------------------------------------------
 // (K2B_BLK, the block size, is in dataplane.h)
 
+// The K2b bodies below serve two layouts of the per-tile arrays (bcount,
+// pprefix, tslot): [NB][W*64] int32 in global scratch, indexed by the user u
+// (stride = W * 64, col = u), and the route kernel's [NB][64] narrow arrays
+// in LDS, one mask word's users indexed by lane (stride = 64, col = lane;
+// RouteLds, tick_geom.h).  `wcol` is the [M] column of mask words of the
+// wave's mask word, in mask_t or in LDS.  Tile (b, user) is at b * stride + col.
+
+// P1 for one tile: how many of block b's messages go to this lane's user.
+__device__ __forceinline__ int k2b_tile_count(const uint64_t* __restrict__ wcol, int32_t M, int b)
+{
+    const uint64_t bit = 1ull << (threadIdx.x & 63);
+    const int m0 = b * K2B_BLK, m1 = min(M, m0 + K2B_BLK);
+    int c = 0;
+    for (int m = m0; m < m1; ++m) c += (wcol[m] & bit) ? 1 : 0;
+    return c;
+}
+
 // P1 body, shared with the fused tick's k2b_p1_count_z.
 __device__ __forceinline__ void k2b_p1_body(
     const uint64_t* __restrict__ mask_t,   // [W][M]
@@ -1057,12 +1094,7 @@ __device__ __forceinline__ void k2b_p1_body(
     if (wave >= W * NB) return;
     const int w = wave / NB, b = wave - (int64_t)(wave / NB) * NB;
     const int lane = threadIdx.x & 63;
-    const uint64_t bit = 1ull << lane;
-    const uint64_t* col = mask_t + (int64_t)w * M;
-    const int m0 = b * K2B_BLK, m1 = min(M, m0 + K2B_BLK);
-    int c = 0;
-    for (int m = m0; m < m1; ++m) c += (col[m] & bit) ? 1 : 0;
-    bcount[(int64_t)b * (W * 64) + (w * 64 + lane)] = c;
+    bcount[(int64_t)b * (W * 64) + (w * 64 + lane)] = k2b_tile_count(mask_t + (int64_t)w * M, M, b);
 }
 
 extern "C" __global__ void k2b_p1_count(
@@ -1080,21 +1112,22 @@ struct K2bUser { int32_t base; int32_t fit; int64_t dst; };
 // totals and block prefixes, the wave-aggregated span claim, the closed-form
 // ring math (cursor advance) and the drop count.  Every lane of the wave
 // must call it (it shuffles); an inactive lane gets zeros back.
+template <class Cnt, class Pre>
 __device__ __forceinline__ K2bUser k2b_p2_body(
-    const int32_t* __restrict__ bcount,    // [NB][W*64]
-    int u, bool active, int32_t W, int32_t NB,
+    const Cnt* __restrict__ bcount,        // tiles
+    int u, bool active, int32_t stride, int col, int32_t NB,
     int64_t ring_bytes, int32_t capacity, int32_t uniform_rec,
     uint64_t* __restrict__ ring_wpos,
     int32_t* __restrict__ n_pairs,
-    int32_t* __restrict__ pprefix,         // [NB][W*64] out: per-block p-offset
+    Pre* __restrict__ pprefix,             // tiles, out: per-block p-offset
     uint32_t* __restrict__ drops)
 {
     const int lane = threadIdx.x & 63;
     int total = 0;
     if (active) {
         for (int b = 0; b < NB; ++b) {
-            pprefix[(int64_t)b * (W * 64) + u] = total;
-            total += bcount[(int64_t)b * (W * 64) + u];
+            pprefix[(int64_t)b * stride + col] = (Pre)total;
+            total += bcount[(int64_t)b * stride + col];
         }
     }
     // the contiguous per-user span; inactive lanes carry total = 0 through it
@@ -1129,8 +1162,8 @@ extern "C" __global__ void k2b_p2_bases(
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = u < n_users;
-    const K2bUser r = k2b_p2_body(bcount, u, active, W, NB, ring_bytes, capacity, uniform_rec,
-                                  ring_wpos, n_pairs, pprefix, drops);
+    const K2bUser r = k2b_p2_body(bcount, u, active, W * 64, u, NB, ring_bytes, capacity,
+                                  uniform_rec, ring_wpos, n_pairs, pprefix, drops);
     if (active) {
         ubase[u] = r.base;
         ufit[u] = r.fit;
@@ -1195,6 +1228,8 @@ extern "C" void launch_k2b_blocks_t(
                        mask_t, pprefix, ubase, ufit, udst, M, W, NB, n_users,
                        capacity, uniform_rec, pairs);
 }
+
+extern "C" {
 
 void launch_k2b_fused_t(const uint64_t* mask_t, const int32_t* payload_len, int32_t M,
                         int32_t W, int32_t n_users, int64_t ring_bytes, int32_t capacity,
@@ -1504,18 +1539,28 @@ void launch_k6_direct_apply(uint64_t* table_keys, int32_t* table_vals, int64_t t
 // message the same wire length, no Direct routing, no peer slots, no
 // by-reference records) runs as ONE launcher call:
 //
-//   K4  k4_parse_batch, K2a k2a_topic_mask_t   as everywhere, into scratch
-//   P1  k2b_p1_count_z   P1, and zeroes the tick's two counters
-//   P2  k2b_p2_tiles     P2 (same claims, cursors and drops), then sorts each
-//                        (user, 32-message block) TILE into dense or sparse
-//   P3  k2b_p3_sparse    pair records for the sparse tiles only
-//   K3d k3d_image + k3_fanout_dense   the dense tiles, from registers
-//   K3  k3_fanout_flat_t    the sparse list (flat2, as on the per-op path)
+//   k_tick_prologue   K4 into scratch, the dense fan-out's record image, and
+//                     the tick's two counters zeroed: all that reads only
+//                     the batch
+//   k_route_word      K2a, P1, P2 (same claims, cursors and drops) with the
+//                     sort of each (user, 32-message block) TILE into dense
+//                     or sparse, and P3's pair records for the sparse tiles
+//                     only; one workgroup per mask word, tiles in LDS
+//   K3d k3_fanout_dense    the dense tiles, from registers
+//   K3  k3_fanout_flat_t   the sparse list (flat2, as on the per-op path)
+//
+// Two launches stand ahead of the dense fan-out because the step starts on
+// an empty queue and every launch ahead of it is host time the GPU waits
+// out (profiles/route_kernel_stats_before.txt: six launches of 2.5 - 9 us
+// each started 8 - 9 us apart).  A batch above ROUTE_MAX_M messages routes
+// by the chain the route kernel merges, with the tiles in scratch:
+// k2a_topic_mask_t, k2b_p1_count_z (P1; zeroes the counters again),
+// k2b_p2_tiles (P2 and the tile sort), k2b_p3_sparse.
 //
 // A tile is DENSE when its user takes every message of the block and all of
 // them are delivered (they fit the ring and lie within pair capacity).  The
 // bytes such a tile puts into the ring are the block's records back to back
-// — the same bytes for every dense user — so k3d_image builds the tick's
+// — the same bytes for every dense user — so the prologue builds the tick's
 // record image once and K3d loads a chunk of it per workgroup and stores it
 // to one user after another: one store instruction per KiB and nothing else
 // in the loop, where the flat kernel spends a pair load, an offset load, a
@@ -1540,6 +1585,50 @@ extern "C" __global__ void k2b_p1_count_z(
     k2b_p1_body(mask_t, M, W, NB, bcount);
 }
 
+// What the tile sort settles for one user (lane): how many records are
+// delivered at most, the user's first sparse-list slot, and where its first
+// record goes.
+struct K2bTiles { int32_t lim; int32_t sbase; int64_t dst; };
+
+// P2 and the tile sort, shared by k2b_p2_tiles and the route kernel: P2's
+// claim, cursor advance and drop count (k2b_p2_body), then every tile of the
+// user classified dense or sparse, tdst and tslot written, and the user's
+// span of the sparse list claimed.  Every lane of the wave must call it.
+// tdst is always the global [NB][W*64] array: the dense fan-out reads it.
+template <class Cnt, class Pre, class Slot>
+__device__ __forceinline__ K2bTiles k2b_tiles_body(
+    const Cnt* __restrict__ bcount,        // tiles
+    int u, bool active, int32_t stride, int col, int32_t M, int32_t W, int32_t NB,
+    int64_t ring_bytes, int32_t capacity, int32_t uniform_rec, int32_t use_dense,
+    uint64_t* __restrict__ ring_wpos,
+    int32_t* __restrict__ n_pairs,
+    int32_t* __restrict__ n_sparse,
+    Pre* __restrict__ pprefix,             // tiles, out
+    Slot* __restrict__ tslot,              // tiles, out
+    int64_t* __restrict__ tdst,            // [NB][W*64] out
+    uint32_t* __restrict__ drops)
+{
+    const K2bUser r = k2b_p2_body(bcount, u, active, stride, col, NB, ring_bytes, capacity,
+                                  uniform_rec, ring_wpos, n_pairs, pprefix, drops);
+    int cap_room = capacity - r.base; if (cap_room < 0) cap_room = 0;
+    const int lim = r.fit < cap_room ? r.fit : cap_room;
+    int n_sp = 0;
+    if (active) {
+        int p = 0;
+        for (int b = 0; b < NB; ++b) {
+            const int64_t i = (int64_t)b * stride + col;
+            const int cnt = bcount[i];
+            const int nm = min(M - b * K2B_BLK, K2B_BLK);
+            const bool dense = use_dense && cnt == nm && p + cnt <= lim;
+            tdst[(int64_t)b * (W * 64) + u] = dense ? r.dst + (int64_t)p * uniform_rec : -1;
+            tslot[i] = (Slot)n_sp;
+            if (!dense) n_sp += max(0, min(cnt, lim - p));
+            p += cnt;
+        }
+    }
+    return K2bTiles{lim, wave_claim_span(n_sp, n_sparse), r.dst};
+}
+
 extern "C" __global__ void k2b_p2_tiles(
     const int32_t* __restrict__ bcount,    // [NB][W*64]
     int32_t M, int32_t W, int32_t NB, int32_t n_users,
@@ -1557,28 +1646,12 @@ extern "C" __global__ void k2b_p2_tiles(
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = u < n_users;
-    const K2bUser r = k2b_p2_body(bcount, u, active, W, NB, ring_bytes, capacity, uniform_rec,
-                                  ring_wpos, n_pairs, pprefix, drops);
-    int cap_room = capacity - r.base; if (cap_room < 0) cap_room = 0;
-    const int lim = r.fit < cap_room ? r.fit : cap_room;
-    int n_sp = 0;
+    const K2bTiles r = k2b_tiles_body(bcount, u, active, W * 64, u, M, W, NB, ring_bytes, capacity,
+                                      uniform_rec, use_dense, ring_wpos, n_pairs, n_sparse,
+                                      pprefix, tslot, tdst, drops);
     if (active) {
-        int p = 0;
-        for (int b = 0; b < NB; ++b) {
-            const int64_t i = (int64_t)b * (W * 64) + u;
-            const int cnt = bcount[i];
-            const int nm = min(M - b * K2B_BLK, K2B_BLK);
-            const bool dense = use_dense && cnt == nm && p + cnt <= lim;
-            tdst[i] = dense ? r.dst + (int64_t)p * uniform_rec : -1;
-            tslot[i] = n_sp;
-            if (!dense) n_sp += max(0, min(cnt, lim - p));
-            p += cnt;
-        }
-    }
-    const int sbase = wave_claim_span(n_sp, n_sparse);
-    if (active) {
-        ulim[u] = lim;
-        usbase[u] = sbase;
+        ulim[u] = r.lim;
+        usbase[u] = r.sbase;
         udst[u] = r.dst;
     }
 }
@@ -1588,38 +1661,40 @@ extern "C" __global__ void k2b_p2_tiles(
 // spread over the block's MESSAGES, so a tile's pairs are stored side by
 // side (ballot + popcount give the slot) and not one lane per user at a
 // 4 KiB stride.  All tiles dense or empty: the wave leaves after the ballot.
-extern "C" __global__ void k2b_p3_sparse(
-    const uint64_t* __restrict__ mask_t,   // [W][M]
-    const int32_t* __restrict__ bcount,
-    const int32_t* __restrict__ pprefix,
-    const int32_t* __restrict__ tslot,
+// The body for the wave's (mask word w, block b), shared by k2b_p3_sparse and
+// the route kernel.  The per-user arrays (ulim, usbase, udst) are indexed by
+// `col` like the tiles; tdst is the global [NB][W*64] array.
+template <class Cnt, class Pre, class Slot>
+__device__ __forceinline__ void k2b_p3_sparse_body(
+    const uint64_t* __restrict__ wcol,     // [M] mask words of word w
+    const Cnt* __restrict__ bcount,
+    const Pre* __restrict__ pprefix,
+    const Slot* __restrict__ tslot,
     const int64_t* __restrict__ tdst,
     const int32_t* __restrict__ ulim,
     const int32_t* __restrict__ usbase,
     const int64_t* __restrict__ udst,
-    int32_t M, int32_t W, int32_t NB, int32_t n_users, int32_t uniform_rec,
+    int w, int b, int32_t stride, int col,
+    int32_t M, int32_t W, int32_t n_users, int32_t uniform_rec,
     PairRec* __restrict__ pairs)
 {
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (wave >= W * NB) return;
-    const int w = wave / NB, b = wave - (wave / NB) * NB;
     const int lane = threadIdx.x & 63;
     const int u = w * 64 + lane;
     int p0 = 0, lim = 0, slot0 = 0;
     int64_t dstb = 0;
     bool sparse = false;
     if (u < n_users) {
-        const int64_t i = (int64_t)b * (W * 64) + u;
+        const int64_t i = (int64_t)b * stride + col;
         p0 = pprefix[i];
-        lim = ulim[u];
-        sparse = tdst[i] < 0 && bcount[i] > 0 && p0 < lim;
-        slot0 = usbase[u] + tslot[i];
-        dstb = udst[u];
+        lim = ulim[col];
+        sparse = tdst[(int64_t)b * (W * 64) + u] < 0 && bcount[i] > 0 && p0 < lim;
+        slot0 = usbase[col] + tslot[i];
+        dstb = udst[col];
     }
     unsigned long long todo = __ballot(sparse);
     if (!todo) return;
     const int m0 = b * K2B_BLK, nm = min(M - m0, K2B_BLK);
-    const uint64_t word = lane < nm ? mask_t[(int64_t)w * M + m0 + lane] : 0ull;
+    const uint64_t word = lane < nm ? wcol[m0 + lane] : 0ull;
     while (todo) {
         const int j = __ffsll((long long)todo) - 1;
         todo &= todo - 1;
@@ -1636,24 +1711,130 @@ extern "C" __global__ void k2b_p3_sparse(
     }
 }
 
+extern "C" __global__ void k2b_p3_sparse(
+    const uint64_t* __restrict__ mask_t,   // [W][M]
+    const int32_t* __restrict__ bcount,
+    const int32_t* __restrict__ pprefix,
+    const int32_t* __restrict__ tslot,
+    const int64_t* __restrict__ tdst,
+    const int32_t* __restrict__ ulim,
+    const int32_t* __restrict__ usbase,
+    const int64_t* __restrict__ udst,
+    int32_t M, int32_t W, int32_t NB, int32_t n_users, int32_t uniform_rec,
+    PairRec* __restrict__ pairs)
+{
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (wave >= W * NB) return;
+    const int w = wave / NB, b = wave - (wave / NB) * NB;
+    k2b_p3_sparse_body(mask_t + (int64_t)w * M, bcount, pprefix, tslot, tdst, ulim, usbase, udst,
+                       w, b, W * 64, w * 64 + (int)(threadIdx.x & 63), M, W, n_users,
+                       uniform_rec, pairs);
+}
+
+// The route kernel: K2a, P1, P2 with the tile sort, and P3 for ONE mask word
+// (64 users) per workgroup, in one launch.  Everything those four kernels
+// hand each other depends on the user's own mask word only, so it stays in
+// LDS (RouteLds, tick_geom.h) and the phases are separated by workgroup
+// barriers where the chain has launch boundaries.  Across workgroups there
+// are only the n_pairs / n_sparse / drops atomics, as in the chain.  P2 is
+// one wave's work (a lane per user); the other phases are spread over the
+// workgroup's waves.  The bodies are the chain's own.
+extern "C" __global__ void __launch_bounds__(ROUTE_THREADS) k_route_word(
+    const uint64_t* __restrict__ sub_bitmap,  // [256][W]
+    const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ topics_off,
+    const int32_t* __restrict__ topics_cnt,
+    const int32_t* __restrict__ disc,
+    int32_t M, int32_t W, int32_t NB, int32_t n_users,
+    int64_t ring_bytes, int32_t capacity, int32_t uniform_rec, int32_t use_dense,
+    uint64_t* __restrict__ ring_wpos,
+    int32_t* __restrict__ n_pairs,
+    int32_t* __restrict__ n_sparse,
+    int64_t* __restrict__ tdst,               // [NB][W*64] out: dense tile ring address, or -1
+    PairRec* __restrict__ pairs,
+    uint32_t* __restrict__ drops)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t route_smem[];
+    const RouteLds l = route_lds(M);
+    uint64_t* wcol = (uint64_t*)(route_smem + l.mask);
+    int64_t* udst = (int64_t*)(route_smem + l.udst);
+    int32_t* ulim = (int32_t*)(route_smem + l.ulim);
+    int32_t* usbase = (int32_t*)(route_smem + l.usbase);
+    uint16_t* pprefix = (uint16_t*)(route_smem + l.pprefix);
+    uint16_t* tslot = (uint16_t*)(route_smem + l.tslot);
+    uint8_t* bcount = route_smem + l.bcount;
+
+    const int w = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    const int u = w * 64 + lane;
+
+    // K2a
+    for (int m = threadIdx.x; m < M; m += blockDim.x)
+        wcol[m] = topic_row_or<false>(sub_bitmap, buf, topics_off, topics_cnt, disc, m, w, W,
+                                      nullptr, 0);
+    __syncthreads();
+    // P1
+    for (int b = wave; b < NB; b += n_waves)
+        bcount[b * 64 + lane] = (uint8_t)k2b_tile_count(wcol, M, b);
+    __syncthreads();
+    // P2 and the tile sort: the whole of wave 0, inactive users included
+    if (wave == 0) {
+        const bool active = u < n_users;
+        const K2bTiles r = k2b_tiles_body(bcount, u, active, 64, lane, M, W, NB, ring_bytes,
+                                          capacity, uniform_rec, use_dense, ring_wpos, n_pairs,
+                                          n_sparse, pprefix, tslot, tdst, drops);
+        ulim[lane] = r.lim;
+        usbase[lane] = r.sbase;
+        udst[lane] = r.dst;
+    }
+    // also makes wave 0's tdst stores visible to the other waves' loads below
+    __syncthreads();
+    // P3
+    for (int b = wave; b < NB; b += n_waves)
+        k2b_p3_sparse_body(wcol, bcount, pprefix, tslot, tdst, ulim, usbase, udst, w, b, 64, lane,
+                           M, W, n_users, uniform_rec, pairs);
+}
+
 // The record image: the M records of this tick, back to back at full stride,
 // exactly the bytes the flat kernel stores for each of them — header
 // {len, seq_base + m, 0, 0}, then payload_unit values.  One thread per unit,
 // so a misaligned source or a partial tail is handled once per image unit
 // and not once per delivery; K3d then only does aligned dword4 loads.
-extern "C" __global__ void k3d_image(
+__device__ __forceinline__ void k3d_image_body(
     const uint8_t* __restrict__ buf,
     const int64_t* __restrict__ offsets,   // [M+1]
     int32_t M, int32_t units_per_rec, uint32_t div_magic, int32_t div_shift,
     int32_t uniform_len, uint32_t seq_base,
-    cdn_v4u* __restrict__ image)           // [M * units_per_rec]
+    cdn_v4u* __restrict__ image,           // [M * units_per_rec]
+    uint32_t i)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (uint32_t)(M * units_per_rec)) return;
     const int m = (int)(((uint64_t)i * div_magic) >> div_shift);
     const int q = (int)i - m * units_per_rec;
     image[i] = q == 0 ? cdn_v4u{(uint32_t)uniform_len, seq_base + (uint32_t)m, 0u, 0u}
                       : payload_unit(buf + offsets[m], (q - 1) * 16, uniform_len);
+}
+
+// The prologue: everything of the tick that reads only the batch itself, in
+// one launch.  The first parse_blocks workgroups parse (K4, a thread per
+// message), the rest build the record image (a thread per unit; none when
+// the dense fan-out is off), and the first thread zeroes the tick's two
+// counters, which the route kernel, the next launch, claims from.
+extern "C" __global__ void __launch_bounds__(256) k_tick_prologue(
+    const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ offsets,   // [M+1]
+    int32_t M, uint64_t hash_seed, ParseOut out, int32_t parse_blocks,
+    int32_t units_per_rec, uint32_t div_magic, int32_t div_shift,
+    int32_t uniform_len, uint32_t seq_base,
+    cdn_v4u* __restrict__ image,
+    int32_t* __restrict__ n_pairs, int32_t* __restrict__ n_sparse)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) { *n_pairs = 0; *n_sparse = 0; }
+    if ((int32_t)blockIdx.x < parse_blocks)
+        k4_parse_body(buf, offsets, M, hash_seed, out, blockIdx.x * blockDim.x + threadIdx.x);
+    else
+        k3d_image_body(buf, offsets, M, units_per_rec, div_magic, div_shift, uniform_len, seq_base,
+                       image, (blockIdx.x - parse_blocks) * blockDim.x + threadIdx.x);
 }
 
 // K3d.  blockIdx.x = (group * NB + block) * n_chunks + chunk: a workgroup
@@ -1736,30 +1917,46 @@ void launch_tick_uniform_broadcast(const UniformTick* t, hipStream_t s) {
     int32_t* ulim = p32;         p32 += U;
     int32_t* usbase = p32;
 
-    launch_k4_parse(t->buf, t->offsets, M, t->hash_seed,
-                    ParseOut{disc, payload_off, payload_len, topics_off, topics_cnt,
-                             (uint64_t*)recip_hash, (uint64_t*)timestamp}, s);
-    launch_k2a_topic_mask_t(t->sub_bitmap, t->buf, topics_off, topics_cnt, disc, mask_t, M, W, s);
-
+    // 1. the prologue: parse, record image, counters zeroed
     const int threads = 256;
-    const int blocks_wb = (W * NB * 64 + threads - 1) / threads;
-    const int blocks_u = (t->n_users + threads - 1) / threads;
-    hipLaunchKernelGGL(k2b_p1_count_z, dim3(blocks_wb), dim3(threads), 0, s, mask_t, M, W, NB,
-                       bcount, t->n_pairs, t->n_sparse);
-    hipLaunchKernelGGL(k2b_p2_tiles, dim3(blocks_u), dim3(threads), 0, s, bcount, M, W, NB,
-                       t->n_users, t->ring_bytes, t->capacity, t->rec, t->dense ? 1 : 0,
-                       t->ring_wpos, t->n_pairs, t->n_sparse, pprefix, tslot, tdst, ulim, usbase,
-                       udst, t->drops);
-    hipLaunchKernelGGL(k2b_p3_sparse, dim3(blocks_wb), dim3(threads), 0, s, mask_t, bcount,
-                       pprefix, tslot, tdst, ulim, usbase, udst, M, W, NB, t->n_users, t->rec,
-                       t->pairs);
+    const int parse_blocks = (M + threads - 1) / threads;
+    const int image_blocks = t->dense ? (M * units + threads - 1) / threads : 0;
+    uint32_t dm; int32_t dsh;
+    u32_div_magic(units, &dm, &dsh);
+    hipLaunchKernelGGL(k_tick_prologue, dim3(parse_blocks + image_blocks), dim3(threads), 0, s,
+                       t->buf, t->offsets, M, t->hash_seed,
+                       ParseOut{disc, payload_off, payload_len, topics_off, topics_cnt,
+                                (uint64_t*)recip_hash, (uint64_t*)timestamp},
+                       parse_blocks, units, dm, dsh, t->uniform_len, t->seq_base, image,
+                       t->n_pairs, t->n_sparse);
+
+    // 2. routing: one launch, or for a batch whose mask column does not fit
+    // a workgroup's LDS the chain of four through scratch
+    if (M <= ROUTE_MAX_M) {
+        hipLaunchKernelGGL(k_route_word, dim3(W), dim3(ROUTE_THREADS), route_lds(M).bytes, s,
+                           t->sub_bitmap, t->buf, topics_off, topics_cnt, disc, M, W, NB,
+                           t->n_users, t->ring_bytes, t->capacity, t->rec, t->dense ? 1 : 0,
+                           t->ring_wpos, t->n_pairs, t->n_sparse, tdst, t->pairs, t->drops);
+    } else {
+        launch_k2a_topic_mask_t(t->sub_bitmap, t->buf, topics_off, topics_cnt, disc, mask_t, M, W,
+                                s);
+        const int blocks_wb = (W * NB * 64 + threads - 1) / threads;
+        const int blocks_u = (t->n_users + threads - 1) / threads;
+        // zeroes the two counters once more, still ahead of P2's first claim
+        hipLaunchKernelGGL(k2b_p1_count_z, dim3(blocks_wb), dim3(threads), 0, s, mask_t, M, W, NB,
+                           bcount, t->n_pairs, t->n_sparse);
+        hipLaunchKernelGGL(k2b_p2_tiles, dim3(blocks_u), dim3(threads), 0, s, bcount, M, W, NB,
+                           t->n_users, t->ring_bytes, t->capacity, t->rec, t->dense ? 1 : 0,
+                           t->ring_wpos, t->n_pairs, t->n_sparse, pprefix, tslot, tdst, ulim,
+                           usbase, udst, t->drops);
+        hipLaunchKernelGGL(k2b_p3_sparse, dim3(blocks_wb), dim3(threads), 0, s, mask_t, bcount,
+                           pprefix, tslot, tdst, ulim, usbase, udst, M, W, NB, t->n_users, t->rec,
+                           t->pairs);
+    }
+
+    // 3. the fan-out
     if (t->dense) {
         const DenseGeom geo = dense_geom(units);
-        uint32_t dm; int32_t dsh;
-        u32_div_magic(units, &dm, &dsh);
-        hipLaunchKernelGGL(k3d_image, dim3((M * units + threads - 1) / threads), dim3(threads),
-                           0, s, t->buf, t->offsets, M, units, dm, dsh, t->uniform_len,
-                           t->seq_base, image);
         const dim3 grid((uint32_t)(dense_grid_x(t->n_users, DENSE_GROUP, geo.n_chunks) * NB));
         hipLaunchKernelGGL(k3_fanout_dense, grid, dim3(DENSE_THREADS), 0, s, image, tdst, M, NB,
                            (int32_t)U, t->n_users, units, geo.n_chunks, geo.chunk_units,

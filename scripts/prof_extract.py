@@ -2,10 +2,17 @@
 """Extract a per-kernel stats table from rocprofv3 output (rocpd sqlite DB
 or kernel_stats CSV) into the plain-text format committed under profiles/.
 
-Usage: python scripts/prof_extract.py <dir-or-file> [out.txt]
+Usage: python scripts/prof_extract.py <dir-or-file> [out.txt] [--interval KERNEL]
 Introspects the schema (rocprofv3's table/column names move between
 versions) and prints: kernel, calls, total_us, avg_us, %, plus
 vgpr/sgpr/scratch when the symbol table carries them.
+
+From a rocpd DB (which has every dispatch's start and end) it adds a
+timeline table: per kernel, the median duration and the median IDLE time
+before it, i.e. from the end of the dispatch that finished last before it
+to its own start.  With --interval KERNEL it also gives the median interval
+from the end of one KERNEL dispatch to the start of the next, and how much
+of that interval other kernels were running.
 """
 
 import csv
@@ -13,6 +20,10 @@ import glob
 import os
 import sqlite3
 import sys
+
+
+# (start_ns, end_ns, kernel) of every dispatch seen in a DB
+TIMELINE = []
 
 
 def find_inputs(path):
@@ -68,12 +79,48 @@ def extract_db(path):
         dur = (e - s) / 1e3  # ns -> us
         c, t = rows.get(k, (0, 0.0))
         rows[k] = (c + 1, t + dur)
+        TIMELINE.append((s, e, str(names.get(k, k))))
     out = []
     for k, (c, t) in rows.items():
         nm = str(names.get(k, k))
         v = res.get(k, (None,) * 4)
         out.append((nm, c, t, v))
     return out
+
+
+def median(xs):
+    xs = sorted(xs)
+    n = len(xs)
+    return 0.0 if not n else (xs[n // 2] if n % 2 else (xs[n // 2 - 1] + xs[n // 2]) / 2)
+
+
+def timeline_text(interval_kernel):
+    """Per-kernel median duration and idle-before; the interval summary."""
+    tl = sorted(TIMELINE)
+    dur, idle = {}, {}
+    last_end = None
+    for s, e, nm in tl:
+        dur.setdefault(nm, []).append((e - s) / 1e3)
+        if last_end is not None:
+            idle.setdefault(nm, []).append(max(0, s - last_end) / 1e3)
+        last_end = e if last_end is None else max(last_end, e)
+    lines = ["", f"{'kernel (timeline)':<52} {'calls':>6} {'med_dur_us':>11} {'med_idle_before_us':>19}"]
+    for nm in sorted(dur, key=lambda n: -sum(dur[n])):
+        lines.append(f"{nm[:52]:<52} {len(dur[nm]):>6} {median(dur[nm]):>11.2f} "
+                     f"{median(idle.get(nm, [])):>19.2f}")
+    if interval_kernel:
+        marks = [i for i, (_s, _e, nm) in enumerate(tl) if nm.startswith(interval_kernel)]
+        spans, busy = [], []
+        for a, b in zip(marks, marks[1:]):
+            spans.append((tl[b][0] - tl[a][1]) / 1e3)
+            busy.append(sum(e - s for s, e, _nm in tl[a + 1:b]) / 1e3)
+        # the steady state: the second half of the intervals (past the warm-up)
+        spans, busy = spans[len(spans) // 2:], busy[len(busy) // 2:]
+        lines += ["", f"end of {interval_kernel} -> start of the next, median of the last "
+                      f"{len(spans)} intervals: {median(spans):.1f} us, "
+                      f"kernel time inside it {median(busy):.1f} us, "
+                      f"idle {median(spans) - median(busy):.1f} us"]
+    return "\n".join(lines) + "\n"
 
 
 def extract_csv(path):
@@ -88,6 +135,11 @@ def extract_csv(path):
 
 
 def main():
+    interval_kernel = None
+    if "--interval" in sys.argv:
+        k = sys.argv.index("--interval")
+        interval_kernel = sys.argv[k + 1]
+        del sys.argv[k:k + 2]
     path = sys.argv[1]
     inputs = find_inputs(path)
     if not inputs:
@@ -108,6 +160,8 @@ def main():
         lines.append(f"{nm[:52]:<52} {c:>6} {t:>11.1f} {t / c:>9.2f} "
                      f"{t / total * 100:>5.1f}% {vg:>5} {ag:>5} {sg:>5} {scr:>9}")
     text = "\n".join(lines) + "\n"
+    if TIMELINE:
+        text += timeline_text(interval_kernel)
     print(text)
     if len(sys.argv) > 2:
         with open(sys.argv[2], "w") as f:
