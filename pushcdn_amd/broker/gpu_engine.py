@@ -157,6 +157,12 @@ class GpuBrokerEngine:
         # value (apply_direct_updates deletes); cleared by every rebuild
         self._direct_tombstones: set = set()
         self._direct_failed = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the membership log (see queue_join): recipient -> [clear, set, reset]
+        # with 256-bit topic sets as ints, and routing hash -> (owner or None
+        # for a delete, whether the device table held the hash beforehand)
+        self._mship_rows: Dict[int, list] = {}
+        self._mship_direct: Dict[int, Tuple[Optional[int], bool]] = {}
+        self._ctl_ops = None  # pushcdn_gpu_ctl, loaded by the first flush
         # by-reference delivery (None = off: exactly the inline kernels).
         # Needs fanout_wire, so that host and device both know a message's
         # fanned-out length from the batch offsets alone; every message
@@ -195,12 +201,14 @@ class GpuBrokerEngine:
     # ---------------- subscription management (host-driven) ----------------
 
     def subscribe(self, user_idx: int, topics: List[int]) -> None:
+        self.flush_membership()
         w, bit = user_idx >> 6, 1 << (user_idx & 63)
         bit = bit - (1 << 64) if bit >= (1 << 63) else bit
         for t in topics:
             self.sub_bitmap[t & 0xFF, w] |= bit
 
     def unsubscribe(self, user_idx: int, topics: List[int]) -> None:
+        self.flush_membership()
         w, bit = user_idx >> 6, 1 << (user_idx & 63)
         bit = bit - (1 << 64) if bit >= (1 << 63) else bit
         for t in topics:
@@ -208,6 +216,7 @@ class GpuBrokerEngine:
 
     def subscribe_all(self, topics: List[int]) -> None:
         """Subscribe every user to the given topics (bulk, for benches)."""
+        self.flush_membership()
         if self.n_peer_slots:
             # user bits only: peer-slot bits of the row are kept
             full = self._user_bit_words().to(self.device)
@@ -244,6 +253,7 @@ class GpuBrokerEngine:
     def set_peer_topics(self, p: int, topics: List[int]) -> None:
         """Make `topics` the exact interest set of peer slot p: a local
         Broadcast on any of them lands once in ring n_users + p."""
+        self.flush_membership()
         w, bit = self._peer_word_bit(p)
         self.sub_bitmap[:, w] &= ~bit
         rows = sorted({t & 0xFF for t in topics})
@@ -255,6 +265,7 @@ class GpuBrokerEngine:
         whatever the ring still holds is discarded.  Its DirectMap entries
         are the caller's to delete (direct_keys_owned_by +
         apply_direct_updates)."""
+        self.flush_membership()
         w, bit = self._peer_word_bit(p)
         self.sub_bitmap[:, w] &= ~bit
         self.ring_wpos[self.n_users + p] = 0
@@ -273,6 +284,7 @@ class GpuBrokerEngine:
 
     def register_direct(self, pubkey: bytes, owner: int) -> None:
         """owner >= 0: local user index. owner <= -2: peer slot -(p+2)."""
+        self.flush_membership()
         h = self._direct_hash(pubkey)
         self._direct_pubkeys[h] = pubkey
         self._direct_entries[h] = owner
@@ -280,6 +292,7 @@ class GpuBrokerEngine:
 
     def register_direct_bulk(self, entries) -> None:
         """Register many (pubkey, owner) pairs with one table rebuild."""
+        self.flush_membership()
         for pubkey, owner in entries:
             h = self._direct_hash(pubkey)
             self._direct_pubkeys[h] = pubkey
@@ -289,6 +302,7 @@ class GpuBrokerEngine:
     def unregister_direct(self, pubkey: bytes) -> None:
         """Remove a departed user's entry so a Direct to their key is dropped
         instead of delivered to whoever reuses the slot."""
+        self.flush_membership()
         h = fnv1a64(pubkey, self.hash_seed)
         if self._direct_entries.pop(h, None) is not None:
             self._direct_pubkeys.pop(h, None)
@@ -297,6 +311,7 @@ class GpuBrokerEngine:
     def subscribe_modulo(self, n_topics: int) -> None:
         """Bulk: user u subscribes to topic (u % n_topics) — the mixed-bench
         population shape. Vectorized bitmap build on host, one H2D copy."""
+        self.flush_membership()
         import numpy as np
 
         bitmap = np.zeros((256, self.W), dtype=np.uint64)
@@ -343,6 +358,7 @@ class GpuBrokerEngine:
         table is compacted by a rebuild.
         Raises RuntimeError("direct table full") if the live entries alone
         do not fit."""
+        self.flush_membership()
         ups: Dict[int, Tuple[bytes, int]] = {}
         for pubkey, owner in upserts:
             h = fnv1a64(pubkey, self.hash_seed)
@@ -366,18 +382,25 @@ class GpuBrokerEngine:
             1 for h in ups if h not in self._direct_entries)
         if live > S:
             raise RuntimeError("direct table full")
-        new_slots = sum(1 for h in ups if h not in self._direct_entries
-                        and h not in self._direct_tombstones)
-        used = len(self._direct_entries) + len(self._direct_tombstones) + new_slots
         for h in dels:
             del self._direct_entries[h]
             del self._direct_pubkeys[h]
         for h, (pubkey, owner) in ups.items():
             self._direct_entries[h] = owner
             self._direct_pubkeys[h] = pubkey
-        if not ups and not dels:
+        self._push_direct([(h, o) for h, (_k, o) in ups.items()], dels)
+
+    def _push_direct(self, up_list: List[Tuple[int, int]], dels: List[int]) -> None:
+        """Bring the device table in line with the host dicts, which already
+        hold the change: `up_list` is (hash, owner) upserts, `dels` hashes to
+        tombstone, all distinct.  One K6 launch (or the CPU mirror), or a
+        rebuild where the tombstone rule or a failed insert asks for one."""
+        if not up_list and not dels:
             return
-        tombstones = (self._direct_tombstones | set(dels)) - set(ups)
+        S = self.direct_keys.shape[0]
+        tombstones = (self._direct_tombstones | set(dels)) - {h for h, _ in up_list}
+        # slots in use once this batch is in: live entries + tombstones
+        used = len(self._direct_entries) + len(tombstones)
         # compaction reclaims tombstoned slots only: with none, a table past
         # half full keeps taking incremental inserts (probe chains grow, as
         # in any open-addressing table; size gpu_direct_table_size at twice
@@ -387,7 +410,6 @@ class GpuBrokerEngine:
             self._rebuild_direct_table()
             return
         self._direct_tombstones = tombstones
-        up_list = [(h, o) for h, (_k, o) in ups.items()]
         try:
             if not self.use_gpu_ops:
                 from ..ops.reference import direct_apply
@@ -405,7 +427,11 @@ class GpuBrokerEngine:
                 del_keys = torch.tensor([i64(h) for h in dels], dtype=torch.int64).to(dev)
                 self._ops.direct_apply(self.direct_keys, self.direct_vals, up_keys,
                                        up_owners, del_keys, self._direct_failed)
-                failed = int(self._direct_failed.cpu()[0])  # control path only
+                # A 4-byte readback, also on a tick whose membership flush
+                # carries DirectMap changes: an insert that found no slot has
+                # to be repaired by the rebuild below BEFORE that tick's K5
+                # looks the key up.
+                failed = int(self._direct_failed.cpu()[0])
                 if failed:
                     self._direct_failed.zero_()
         except Exception:
@@ -415,6 +441,130 @@ class GpuBrokerEngine:
             raise
         if failed:
             self._rebuild_direct_table()
+
+    # ---------------------------- membership log ----------------------------
+    #
+    # queue_* record user joins, leaves and subscription changes on the host;
+    # flush_membership() applies everything pending with one K8 launch
+    # (bitmap bits + ring cursors) and one K6 launch (DirectMap).  The log is
+    # kept COALESCED: one row (clear, set, reset) per recipient and one
+    # pending upsert/delete per routing hash, folded in program order, so it
+    # never holds more than n_recipients rows whatever the churn.  tick(),
+    # tick_graphed(), every drain_* and every immediate state-changing method
+    # flush first, so mixed use keeps program order.
+
+    _ALL_TOPICS = (1 << 256) - 1
+
+    @property
+    def pending_membership(self) -> int:
+        """Rows the next flush_membership() will apply."""
+        return len(self._mship_rows)
+
+    @staticmethod
+    def _topic_bits(topics) -> int:
+        bits = 0
+        for t in topics:
+            bits |= 1 << (t & 0xFF)
+        return bits
+
+    def _check_recipient(self, r: int, limit: int) -> None:
+        if not 0 <= r < limit:
+            raise IndexError(f"recipient {r} outside [0, {limit})")
+
+    def _queue_row(self, r: int, clear: int, set_: int, replace: bool) -> None:
+        row = self._mship_rows.get(r)
+        if replace:
+            # join / leave: whatever was pending for r is superseded
+            self._mship_rows[r] = [self._ALL_TOPICS, set_, True]
+        elif row is None:
+            self._mship_rows[r] = [clear, set_, False]
+        else:
+            row[0] = (row[0] | clear) & ~set_
+            row[1] = (row[1] | set_) & ~clear
+
+    def _queue_direct(self, h: int, owner: Optional[int]) -> None:
+        """owner None = delete.  Remembers whether the device table held the
+        hash before the first pending change, so a delete of an entry that
+        never reached the device is dropped at flush."""
+        prev = self._mship_direct.get(h)
+        on_device = prev[1] if prev is not None else h in self._direct_entries
+        self._mship_direct[h] = (owner, on_device)
+
+    def queue_subscribe(self, recipient: int, topics: List[int]) -> None:
+        self._check_recipient(recipient, self.n_recipients)
+        self._queue_row(recipient, 0, self._topic_bits(topics), False)
+
+    def queue_unsubscribe(self, recipient: int, topics: List[int]) -> None:
+        self._check_recipient(recipient, self.n_recipients)
+        self._queue_row(recipient, self._topic_bits(topics), 0, False)
+
+    def queue_join(self, slot: int, pubkey: bytes, topics: List[int]) -> None:
+        """A user takes `slot`: its interest becomes exactly `topics`, its
+        ring cursor is reset, hash(pubkey) -> slot is upserted.  Raises
+        ValueError on a routing-hash collision with a different registered
+        key and RuntimeError when the DirectMap is full; a refusal leaves
+        the log and the host dicts untouched."""
+        self._check_recipient(slot, self.n_users)
+        h = self._direct_hash(pubkey)
+        if h == 0:
+            raise ValueError("routing hash 0 is the empty marker; refusing registration")
+        if h not in self._direct_entries \
+                and len(self._direct_entries) >= self.direct_keys.shape[0]:
+            raise RuntimeError("direct table full")
+        self._queue_direct(h, slot)
+        self._direct_pubkeys[h] = pubkey
+        self._direct_entries[h] = slot
+        self._queue_row(slot, 0, self._topic_bits(topics), True)
+
+    def queue_leave(self, slot: int, pubkey: Optional[bytes]) -> None:
+        """The user of `slot` departs: all 256 topics cleared, the cursor
+        reset, and the DirectMap entry deleted if it still belongs to
+        `pubkey` (None: no entry to delete)."""
+        self._check_recipient(slot, self.n_users)
+        if pubkey is not None:
+            h = fnv1a64(pubkey, self.hash_seed)
+            if h in self._direct_entries and self._direct_pubkeys.get(h) == pubkey:
+                self._queue_direct(h, None)
+                del self._direct_entries[h]
+                del self._direct_pubkeys[h]
+        self._queue_row(slot, 0, 0, True)
+
+    def flush_membership(self) -> None:
+        """Apply the pending log: one H2D copy of the rows and one K8 launch
+        (the model on the CPU engine), then the DirectMap changes through
+        the incremental K6 path.  An empty log costs nothing."""
+        if self._mship_rows:
+            import numpy as np
+
+            rows, self._mship_rows = self._mship_rows, {}
+            m64 = (1 << 64) - 1
+            flat = []
+            for r, (clear, set_, reset) in rows.items():
+                flat += [r, 1 if reset else 0,
+                         clear & m64, (clear >> 64) & m64, (clear >> 128) & m64, clear >> 192,
+                         set_ & m64, (set_ >> 64) & m64, (set_ >> 128) & m64, set_ >> 192]
+            recs = torch.from_numpy(
+                np.array(flat, dtype=np.uint64).view(np.int64).reshape(len(rows), 10))
+            try:
+                if self.use_gpu_ops:
+                    if self._ctl_ops is None:
+                        from ..ops import get_gpu_ctl_ops
+
+                        self._ctl_ops = get_gpu_ctl_ops()
+                    self._ctl_ops.membership_apply(self.sub_bitmap, self.ring_wpos,
+                                                   recs.to(self.device))
+                else:
+                    from ..ops.reference import membership_apply
+
+                    membership_apply(self.sub_bitmap, self.ring_wpos, recs)
+            except Exception:
+                self._mship_rows = rows   # nothing applied: the rows stay pending
+                raise
+        if self._mship_direct:
+            pending, self._mship_direct = self._mship_direct, {}
+            up_list = [(h, o) for h, (o, _dev) in pending.items() if o is not None]
+            dels = [h for h, (o, on_device) in pending.items() if o is None and on_device]
+            self._push_direct(up_list, dels)
 
     # ---------------------------- the hot tick ----------------------------
 
@@ -476,6 +626,7 @@ class GpuBrokerEngine:
         With a ref_threshold, host_batch and host_offsets are required on
         both engines: a batch that holds a by-reference message is retained
         until the next drain."""
+        self.flush_membership()
         ref_base = 0
         if self.ref_threshold is not None:
             if host_batch is None or host_offsets is None:
@@ -672,6 +823,7 @@ class GpuBrokerEngine:
         (buf, offsets) pair, replayed thereafter (one host call instead of
         ~8 kernel launches). Requires fanout_wire + uniform records +
         direct_enabled=False (the broadcast-bench shape)."""
+        self.flush_membership()
         assert self.fanout_wire and not self.direct_enabled
         if self.ref_threshold is not None and uniform_wire_len >= self.ref_threshold:
             raise ValueError("tick_graphed carries inline records only: "
@@ -750,6 +902,7 @@ class GpuBrokerEngine:
         """Read back ring cursors (the per-tick notify) and reset them.
         Retained by-reference batches are discarded: the cursors were the
         only way to reach the records that point into them."""
+        self.flush_membership()
         self._discard_ref_batches()
         if self.fused_tick and self.use_gpu_ops and self.is_cuda:
             if self._drain_bufs is None:
@@ -774,6 +927,7 @@ class GpuBrokerEngine:
         the Arc-clone fan-out never copies per recipient either
         (user/sender.rs:16-33).  Retained by-reference batches are discarded
         (use drain_compact_ref to get them)."""
+        self.flush_membership()
         self._discard_ref_batches()
         return self._drain_compact()
 
@@ -783,6 +937,7 @@ class GpuBrokerEngine:
         the retained host batch itself when the drain covers one (no copy),
         the retained batches joined in tick order otherwise, b"" when
         nothing went by reference.  Clears the retained batches."""
+        self.flush_membership()
         batches = self._ref_batches
         self._discard_ref_batches()
         if len(batches) == 1:

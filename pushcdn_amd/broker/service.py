@@ -110,6 +110,13 @@ class BrokerConfig:
     # HBM write, no D2H of the payload, no ring-size limit on the message).
     # None: every delivery is copied into the ring, as before.
     gpu_ref_threshold: Optional[int] = None
+    # batched membership on the GPU plane: user joins, leaves and
+    # Subscribe/Unsubscribe frames go to the engine's coalesced membership
+    # log, which the next tick applies with one K8 launch (bitmap + ring
+    # cursors) and one K6 launch (DirectMap) whatever their number.
+    # Off: each change is applied at once, per topic, with a DirectMap
+    # rebuild per connect and disconnect, as before.
+    gpu_batched_membership: bool = False
 
 
 @dataclass
@@ -348,8 +355,7 @@ class Broker:
             # eviction (reference eviction semantics connections/mod.rs:278-304).
             try:
                 handle.gpu_index = self._claim_gpu_slot(pubkey)
-                self._engine.subscribe(handle.gpu_index, topics)
-                self._engine.register_direct(pubkey, handle.gpu_index)
+                self._gpu_join(handle.gpu_index, pubkey, topics)
             except (RuntimeError, ValueError) as exc:
                 log.warning("refusing user %s: %s", ident(pubkey), exc)
                 await self.remove_user(pubkey)
@@ -408,11 +414,11 @@ class Broker:
                         if d == 5:
                             self.connections.subscribe_user(pubkey, topics)
                             if handle.gpu_index is not None:
-                                self._engine.subscribe(handle.gpu_index, topics)
+                                self._gpu_subscribe(handle.gpu_index, topics)
                         else:
                             self.connections.unsubscribe_user(pubkey, topics)
                             if handle.gpu_index is not None:
-                                self._engine.unsubscribe(handle.gpu_index, topics)
+                                self._gpu_unsubscribe(handle.gpu_index, topics)
                         fwds.append(None)
                     else:
                         raise ConnectionError_("malformed or unexpected frame")
@@ -475,11 +481,11 @@ class Broker:
                         if disc == 5:
                             self.connections.subscribe_user(pubkey, topics)
                             if handle.gpu_index is not None:
-                                self._engine.subscribe(handle.gpu_index, topics)
+                                self._gpu_subscribe(handle.gpu_index, topics)
                         else:
                             self.connections.unsubscribe_user(pubkey, topics)
                             if handle.gpu_index is not None:
-                                self._engine.unsubscribe(handle.gpu_index, topics)
+                                self._gpu_unsubscribe(handle.gpu_index, topics)
                         raw.drop()
                     else:
                         raise ConnectionError_("unexpected message type")
@@ -541,7 +547,7 @@ class Broker:
                         break
                     self.connections.subscribe_user(pubkey, topics)
                     if self._engine is not None and handle.gpu_index is not None:
-                        self._engine.subscribe(handle.gpu_index, topics)
+                        self._gpu_subscribe(handle.gpu_index, topics)
                     raw.drop()
                 elif isinstance(msg, m.Unsubscribe):
                     # pruned like Subscribe: an all-invalid unsubscribe
@@ -552,7 +558,7 @@ class Broker:
                         break
                     self.connections.unsubscribe_user(pubkey, topics)
                     if self._engine is not None and handle.gpu_index is not None:
-                        self._engine.unsubscribe(handle.gpu_index, topics)
+                        self._gpu_unsubscribe(handle.gpu_index, topics)
                     raw.drop()
                 else:
                     break  # unexpected message type: disconnect
@@ -782,13 +788,42 @@ class Broker:
 
     def _release_gpu_slot(self, slot: int) -> None:
         pubkey = self._gpu_user_by_slot.pop(slot, None)
+        self._gpu_leave(slot, pubkey)
+        self._free_gpu_slots.append(slot)
+
+    # The four engine membership changes of a user.  With
+    # gpu_batched_membership they go to the engine's membership log (applied
+    # by the next tick in one batch); without, they are applied at once.
+
+    def _gpu_join(self, slot: int, pubkey: bytes, topics) -> None:
+        if self.config.gpu_batched_membership:
+            self._engine.queue_join(slot, pubkey, topics)
+            return
+        self._engine.subscribe(slot, topics)
+        self._engine.register_direct(pubkey, slot)
+
+    def _gpu_leave(self, slot: int, pubkey: Optional[bytes]) -> None:
+        if self.config.gpu_batched_membership:
+            self._engine.queue_leave(slot, pubkey)
+            return
         if pubkey is not None:
             # drop the direct-table entry: a Direct to the departed key must
             # be dropped, not delivered to the slot's next occupant
             self._engine.unregister_direct(pubkey)
         # clear all subscriptions for the slot
         self._engine.unsubscribe(slot, list(range(256)))
-        self._free_gpu_slots.append(slot)
+
+    def _gpu_subscribe(self, slot: int, topics) -> None:
+        if self.config.gpu_batched_membership:
+            self._engine.queue_subscribe(slot, topics)
+        else:
+            self._engine.subscribe(slot, topics)
+
+    def _gpu_unsubscribe(self, slot: int, topics) -> None:
+        if self.config.gpu_batched_membership:
+            self._engine.queue_unsubscribe(slot, topics)
+        else:
+            self._engine.unsubscribe(slot, topics)
 
     # --- peer slots (gpu_peer_forward): a connected broker as a recipient
     # of the device pipeline ---

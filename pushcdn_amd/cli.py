@@ -61,6 +61,9 @@ def _broker_args(p: argparse.ArgumentParser) -> None:
                    help="GPU data plane: deliver messages of at least this many wire "
                         "bytes by reference (16-byte ring record, bytes sent from the "
                         "host copy); unset = every delivery copied into the ring")
+    p.add_argument("--gpu-batched-membership", action="store_true",
+                   help="GPU data plane: queue user joins, leaves and subscription "
+                        "changes and apply them once per tick in one device batch")
     p.add_argument("--user-transport", choices=["tcp", "tcp-tls", "tcp-native", "quic", "quic-native"],
                    default="tcp", help="user-plane transport (tcp-native = C++ epoll "
                                        "pump; quic[-native] = QUIC-profile over UDP)")
@@ -85,6 +88,7 @@ def cmd_broker(args) -> None:
         data_plane=args.data_plane,
         gpu_device=args.gpu_device,
         gpu_ref_threshold=args.gpu_ref_threshold,
+        gpu_batched_membership=args.gpu_batched_membership,
         user_protocol=_transport(args.user_transport),
         broker_protocol=_transport(args.broker_transport),
     )

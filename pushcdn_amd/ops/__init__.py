@@ -34,3 +34,24 @@ def get_gpu_ops():
         return _gpu_mod
     _gpu_mod = build_gpu()
     return _gpu_mod
+
+
+_gpu_ctl_mod = None
+
+
+def get_gpu_ctl_ops():
+    """The device-state maintenance extension (``pushcdn_gpu_ctl``: K8
+    membership_apply), under the same rule as ``get_gpu_ops()``."""
+    global _gpu_ctl_mod
+    if _gpu_ctl_mod is not None:
+        return _gpu_ctl_mod
+    from .build import GPU_CTL_BUILD_DIR, build_gpu_ctl, load_gpu_ctl_prebuilt
+
+    if (GPU_CTL_BUILD_DIR / "pushcdn_gpu_ctl.so").exists():
+        try:
+            _gpu_ctl_mod = load_gpu_ctl_prebuilt()
+            return _gpu_ctl_mod
+        except ImportError:
+            pass
+    _gpu_ctl_mod = build_gpu_ctl()
+    return _gpu_ctl_mod

@@ -1,8 +1,10 @@
 """In-tree build of the HIP/C++ extensions.
 
-Two modules:
+Three modules:
   - ``pushcdn_gpu``  — CDNA4 data-plane kernels (csrc/hip/*.hip) + torch bindings,
                        compiled for gfx950 only.
+  - ``pushcdn_gpu_ctl`` — device-state maintenance kernels
+                       (csrc/hip/membership.hip) + torch bindings, gfx950 only.
   - ``pushcdn_core`` — host C++ (wire serde, BLS-over-BN254, CRDT) via pybind11.
 
 Everything builds into ``<repo>/build/`` (in-tree, so the .so files travel to
@@ -27,33 +29,61 @@ GPU_SOURCES = [
     CSRC / "hip" / "bls_kernels.hip",
 ]
 
+# Built in a directory of its own: the extension builder keeps one
+# build.ninja per build directory.
+GPU_CTL_BUILD_DIR = BUILD_DIR / "ctl"
+GPU_CTL_SOURCES = [
+    CSRC / "gpu_ctl_bindings.cpp",
+    CSRC / "hip" / "membership.hip",
+]
+
 os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
 
 
-def build_gpu(verbose: bool = False):
-    """Compile (if needed) and load the GPU extension. Returns the module."""
+def _build_torch_ext(name: str, srcs, build_dir: Path, verbose: bool):
     from torch.utils.cpp_extension import load
 
-    BUILD_DIR.mkdir(exist_ok=True)
-    sources = [str(s) for s in GPU_SOURCES if s.exists()]
+    build_dir.mkdir(parents=True, exist_ok=True)
+    sources = [str(s) for s in srcs if s.exists()]
     # ninja's rules for hipcc lack header depfiles: if any shared header is
     # newer than a built object, touch the sources so the rebuild triggers.
-    headers = list((CSRC / "common").glob("*.h")) + list((CSRC / "bls").glob("*.h")) \
+    headers = list(CSRC.glob("*.h")) \
+        + list((CSRC / "common").glob("*.h")) + list((CSRC / "bls").glob("*.h")) \
         + list((CSRC / "wire").glob("*.h")) + list((CSRC / "hip").glob("*.h"))
     if headers:
         newest_h = max(h.stat().st_mtime for h in headers)
-        for src in GPU_SOURCES:
+        for src in srcs:
             if src.exists() and src.stat().st_mtime < newest_h:
                 os.utime(src)
     mod = load(
-        name="pushcdn_gpu",
+        name=name,
         sources=sources,
-        build_directory=str(BUILD_DIR),
+        build_directory=str(build_dir),
         extra_cflags=["-O3", "-std=c++17"],
         extra_cuda_cflags=["-O3", "-std=c++17"],
         verbose=verbose,
     )
     return mod
+
+
+def _load_prebuilt(name: str, so: Path):
+    if not so.exists():
+        raise ImportError(
+            f"{name} extension not built (expected {so}); "
+            "run __graft_entry__.build() first"
+        )
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location(name, so)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    sys.modules[name] = mod
+    return mod
+
+
+def build_gpu(verbose: bool = False):
+    """Compile (if needed) and load the GPU extension. Returns the module."""
+    return _build_torch_ext("pushcdn_gpu", GPU_SOURCES, BUILD_DIR, verbose)
 
 
 def load_gpu_prebuilt():
@@ -62,19 +92,18 @@ def load_gpu_prebuilt():
     Used on GPU boxes where the .so traveled with the snapshot; avoids any
     silent rebuild (and fails loudly if the extension is missing).
     """
-    so = BUILD_DIR / "pushcdn_gpu.so"
-    if not so.exists():
-        raise ImportError(
-            f"pushcdn_gpu extension not built (expected {so}); "
-            "run __graft_entry__.build() first"
-        )
-    import importlib.util
+    return _load_prebuilt("pushcdn_gpu", BUILD_DIR / "pushcdn_gpu.so")
 
-    spec = importlib.util.spec_from_file_location("pushcdn_gpu", so)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    sys.modules["pushcdn_gpu"] = mod
-    return mod
+
+def build_gpu_ctl(verbose: bool = False):
+    """Compile (if needed) and load the device-state maintenance extension
+    (K8 membership_apply). Returns the module."""
+    return _build_torch_ext("pushcdn_gpu_ctl", GPU_CTL_SOURCES, GPU_CTL_BUILD_DIR, verbose)
+
+
+def load_gpu_ctl_prebuilt():
+    """load_gpu_prebuilt for the maintenance extension."""
+    return _load_prebuilt("pushcdn_gpu_ctl", GPU_CTL_BUILD_DIR / "pushcdn_gpu_ctl.so")
 
 
 CORE_SOURCES = [CSRC / "core_bindings.cpp"]

@@ -320,6 +320,40 @@ def apply_subs(
             sub_bitmap[t, w] = _i64(word)
 
 
+MEMBERSHIP_WORDS = 10   # row: r, flags, clear[4], set[4]
+MEMBERSHIP_RESET = 1    # flags bit 0: reset the recipient's ring cursor
+
+
+def membership_apply(
+    sub_bitmap: torch.Tensor,  # int64 [256][W] (bit-cast u64), mutated
+    ring_wpos: torch.Tensor,   # int64 [R], mutated
+    recs: torch.Tensor,        # int64 [n][MEMBERSHIP_WORDS]
+) -> None:
+    """Mirror of k8_membership_apply, serial.  Row = (r, flags, clear[4],
+    set[4]); topic t is bit t & 63 of word t >> 6 of a 256-bit set.  For
+    every topic, bit r of sub_bitmap[t][r >> 6] becomes 1 if `set` has t, 0
+    if only `clear` has t (set wins), and is otherwise untouched; flags bit 0
+    zeroes ring_wpos[r].  A row with r outside [0, R) is skipped whole."""
+    R = ring_wpos.shape[0]
+    u64 = (1 << 64) - 1
+    for row in recs.tolist():
+        r, flags = row[0], row[1]
+        if r < 0 or r >= R:
+            continue
+        w, bit = r >> 6, 1 << (r & 63)
+        col = sub_bitmap[:, w].tolist()   # the recipient's word of every topic
+        for t in range(256):
+            tbit = 1 << (t & 63)
+            # u64 arithmetic, then the two's-complement cast back (bit 63)
+            if row[6 + (t >> 6)] & tbit:
+                col[t] = _i64((col[t] & u64) | bit)
+            elif row[2 + (t >> 6)] & tbit:
+                col[t] = _i64(col[t] & u64 & ~bit)
+        sub_bitmap[:, w] = torch.tensor(col, dtype=torch.int64)
+        if flags & MEMBERSHIP_RESET:
+            ring_wpos[r] = 0
+
+
 def compact_rings(egress: bytes, ring_bytes: int, wpos) -> Tuple[List[int], bytes]:
     """Mirror of k7_compact_rings: every ring's used prefix, concatenated in
     ring order.  Returns (offsets, staging bytes); offsets is the exclusive
