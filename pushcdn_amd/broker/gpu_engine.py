@@ -29,6 +29,12 @@ ref_threshold wire bytes is delivered as a bare 16-byte record
 batch, which the engine retains and drain_compact_ref() hands back as the
 reference buffer ref_off indexes.
 
+Loss accounting (loss_accounting=True): a delivery that does not fit its
+ring, or finds the pair list full, is dropped on the device.  A second
+per-recipient accumulator, demand (int64 [R]), takes the ring bytes every
+tick WANTED to deliver (K9); at a drain demand[r] - ring_wpos[r] is what
+recipient r lost (K10), reported by take_losses().
+
 CPU mode (device="cpu") runs the pure-Python mirrors from ops.reference so
 the engine's semantics are testable without a GPU.
 """
@@ -84,6 +90,7 @@ class GpuBrokerEngine:
         n_peer_slots: int = 0,
         ref_threshold: Optional[int] = None,
         fused_tick: bool = True,
+        loss_accounting: bool = False,
     ) -> None:
         # n_peer_slots (P): peer brokers as recipients of the device
         # pipeline.  The recipient index space is R = n_users + P; peer slot
@@ -178,6 +185,27 @@ class GpuBrokerEngine:
         # tick order, and their total size (the next batch's ref_base)
         self._ref_batches: List[bytes] = []
         self._ref_base = 0
+        # loss accounting (False = off: nothing allocated, no extension
+        # loaded, not one extra launch or copy).  demand[r] accumulates the
+        # ring bytes the ticks wanted to deliver to r since the last drain,
+        # ring_wpos[r] is what they did deliver, and every drain reports the
+        # recipients where the two differ (take_losses).  That covers a full
+        # ring and a full pair list alike.
+        self.loss_accounting = loss_accounting
+        self._acct_ops = None
+        self._losses: Dict[int, int] = {}
+        if loss_accounting:
+            self.demand = torch.zeros(R, dtype=torch.int64, device=dev)
+            if self.use_gpu_ops:
+                from ..ops import get_gpu_acct_ops
+
+                self._acct_ops = get_gpu_acct_ops()
+                # K10's outputs: the (recipient, bytes) list, its length on
+                # the device and in pinned host memory
+                self._lossy = torch.empty((max(R, 1), 2), dtype=torch.int64, device=dev)
+                self._n_lossy = torch.zeros(1, dtype=torch.int32, device=dev)
+                self._n_lossy_host = torch.zeros(1, dtype=torch.int32,
+                                                 pin_memory=self.is_cuda)
         self.seq = 0
         self.total = TickStats()
         self._staging_dev: Optional[torch.Tensor] = None
@@ -269,6 +297,10 @@ class GpuBrokerEngine:
         w, bit = self._peer_word_bit(p)
         self.sub_bitmap[:, w] &= ~bit
         self.ring_wpos[self.n_users + p] = 0
+        if self.loss_accounting:
+            # cursor and demand are reset together: the slot's next occupant
+            # must not inherit a loss
+            self.demand[self.n_users + p] = 0
 
     def _direct_hash(self, pubkey: bytes) -> int:
         """Routing hash of a pubkey, with collision refusal: if a DIFFERENT
@@ -560,6 +592,12 @@ class GpuBrokerEngine:
             except Exception:
                 self._mship_rows = rows   # nothing applied: the rows stay pending
                 raise
+            if self.loss_accounting:
+                # K8 reset these cursors: their demand goes with them
+                reset = [r for r, row in rows.items()
+                         if row[2] and 0 <= r < self.n_recipients]
+                if reset:
+                    self.demand[torch.tensor(reset, dtype=torch.int64).to(self.device)] = 0
         if self._mship_direct:
             pending, self._mship_direct = self._mship_direct, {}
             up_list = [(h, o) for h, (o, _dev) in pending.items() if o is not None]
@@ -690,8 +728,11 @@ class GpuBrokerEngine:
 
     def _fused_tick_ok(self, uniform_wire_len: Optional[int], origin) -> bool:
         """The shape the fused native tick serves: uniform wire records that
-        the flat fan-out takes, broadcast only, one broker, all inline."""
-        return (self.fused_tick and self.fanout_wire and uniform_wire_len is not None
+        the flat fan-out takes, broadcast only, one broker, all inline.
+        Never with loss accounting: the fused tick keeps its mask in LDS, so
+        there is no mask_t for the demand kernel to read."""
+        return (self.fused_tick and not self.loss_accounting
+                and self.fanout_wire and uniform_wire_len is not None
                 and not self.direct_enabled and self.n_peer_slots == 0
                 and origin is None and self.ref_threshold is None
                 and ring_rec(uniform_wire_len) <= self._flat_max_rec)
@@ -758,6 +799,7 @@ class GpuBrokerEngine:
                 ring_len = torch.where(payload_len >= thr, 0, payload_len).to(torch.int32)
         rec = ring_rec(uniform_wire_len) if uniform else 0
         self._assign_emit(ops, mask_t, ring_len, rec, M)
+        owner = None
         if self.direct_enabled:
             # K5 lookup + K5b on-device delivery-pair emission: direct pairs
             # append to the same pair list, all consumed by the single
@@ -773,6 +815,12 @@ class GpuBrokerEngine:
             else:
                 ops.emit_direct(disc, owner, payload_off, ring_len, self.ring_bytes,
                                 self.ring_wpos, self._n_pairs, self._pairs, self._drops)
+        if self._acct_ops is not None and M > 0:
+            # K9: what this tick wanted to deliver, per recipient, from the
+            # inputs K2b and K5b claimed from — one launch, nothing read back
+            self._acct_ops.recipient_demand(
+                self.demand, mask_t, ring_len.contiguous(), disc, owner,
+                origin if peer_plane else None, self.n_users, self.n_peer_slots)
         seq_base = self.seq
         self.seq += M
         nt = 1 if self.nt_fanout else 0
@@ -824,6 +872,10 @@ class GpuBrokerEngine:
         ~8 kernel launches). Requires fanout_wire + uniform records +
         direct_enabled=False (the broadcast-bench shape)."""
         self.flush_membership()
+        if self.loss_accounting:
+            # the warm-up runs the body for real and the captured body has no
+            # demand kernel: neither can be squared with the accounting
+            raise ValueError("tick_graphed does not run with loss_accounting")
         assert self.fanout_wire and not self.direct_enabled
         if self.ref_threshold is not None and uniform_wire_len >= self.ref_threshold:
             raise ValueError("tick_graphed carries inline records only: "
@@ -869,6 +921,10 @@ class GpuBrokerEngine:
             ).to(torch.int32)
         thr = self.ref_threshold
         ring_len = pr.payload_len if thr is None else ref.ring_lengths(pr.payload_len, thr)
+        owner = ref.direct_lookup(self.direct_keys, self.direct_vals, pr.recip_hash)
+        if self.loss_accounting:
+            ref.recipient_demand(mask, ring_len, pr.disc, owner, origin, self.n_users,
+                                 self.n_peer_slots, self.demand)
 
         def fan(p_user, p_msg, p_dst):
             if thr is None:
@@ -887,7 +943,6 @@ class GpuBrokerEngine:
         fan(pair_user, pair_msg, pair_dst)
         # Direct deliveries claim ring space after the broadcasts, in message
         # order: local users and, for local-origin messages, peer slots
-        owner = ref.direct_lookup(self.direct_keys, self.direct_vals, pr.recip_hash)
         d_user, d_msg, d_dst, d_drops = ref.emit_direct_peers(
             pr.disc, owner, origin, ring_len, self.ring_wpos, self.ring_bytes,
             self.n_users, self.n_peer_slots)
@@ -904,6 +959,7 @@ class GpuBrokerEngine:
         only way to reach the records that point into them."""
         self.flush_membership()
         self._discard_ref_batches()
+        self._scan_losses()
         if self.fused_tick and self.use_gpu_ops and self.is_cuda:
             if self._drain_bufs is None:
                 self._drain_bufs = (
@@ -912,9 +968,11 @@ class GpuBrokerEngine:
                 )
             staging, host = self._drain_bufs
             self._ops.drain_cursors(self.ring_wpos, staging, host)  # synchronises
+            self._collect_losses()
             return host.clone()
         wpos = self.ring_wpos.detach().clone().to("cpu")
         self.ring_wpos.zero_()
+        self._collect_losses()
         return wpos
 
     def drain_compact(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -947,6 +1005,7 @@ class GpuBrokerEngine:
         return (*self._drain_compact(), refbuf)
 
     def _drain_compact(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        self._scan_losses()
         if not self.use_gpu_ops:
             wpos = self.ring_wpos.detach().clone()
             self.ring_wpos.zero_()
@@ -962,6 +1021,7 @@ class GpuBrokerEngine:
             return wpos, offsets, staging
         wpos_dev = self.ring_wpos  # read by K7 before the reset below
         wpos = wpos_dev.detach().to("cpu")  # sync: cursor readback
+        self._collect_losses()
         offsets = torch.zeros(self.n_recipients + 1, dtype=torch.int64)
         torch.cumsum(wpos, 0, out=offsets[1:])
         total = int(offsets[-1])
@@ -992,6 +1052,44 @@ class GpuBrokerEngine:
                 self._staging_dev.numel(), dtype=torch.uint8, pin_memory=self.is_cuda)
         host[:total].copy_(self._staging_dev[:total])  # sync D2H
         return wpos, offsets, host[:total]
+
+    # --------------------------- loss accounting ---------------------------
+
+    def _scan_losses(self) -> None:
+        """First step of every drain, before anything reads-and-resets the
+        cursors.  GPU: K10 queues its list and a 4-byte count copy into pinned
+        memory on the engine's stream and does not wait; the drain's own
+        synchronise follows and _collect_losses() then reads the count.
+        CPU: the model, merged at once."""
+        if not self.loss_accounting:
+            return
+        if self._acct_ops is None:
+            from ..ops.reference import loss_scan
+
+            self._merge_losses(loss_scan(self.demand, self.ring_wpos))
+            return
+        self._acct_ops.loss_scan(self.demand, self.ring_wpos, self._lossy, self._n_lossy,
+                                 self._n_lossy_host)
+
+    def _collect_losses(self) -> None:
+        """After the drain's synchronise: the list is copied only when the
+        scan found a lossy recipient (the rare path)."""
+        if self._acct_ops is None:
+            return
+        n = int(self._n_lossy_host[0])
+        if n:
+            self._merge_losses(self._lossy[:n].to("cpu").tolist())
+
+    def _merge_losses(self, rows) -> None:
+        for r, d in rows:
+            self._losses[r] = self._losses.get(r, 0) + d
+
+    def take_losses(self) -> Dict[int, int]:
+        """Recipient index -> ring bytes lost (demanded by the ticks, not
+        delivered), as found by the drains since the previous call; clears
+        the record.  Always empty without loss_accounting."""
+        losses, self._losses = self._losses, {}
+        return losses
 
     def next_staging_index(self) -> int:
         """Which host staging buffer the NEXT drain_compact will fill."""

@@ -71,6 +71,9 @@ class MeshBroker(Broker):
     PEER_FORWARD = False
     # the collective tick delivers inline records only
     REF_DELIVERY = False
+    # the collective tick has its own drain: no loss accounting here, so
+    # config.gpu_overflow_policy has no effect
+    OVERFLOW_POLICY = False
 
     def __init__(self, config: BrokerConfig, batch_capacity: int = 1 << 22,
                  interest_routed: Optional[bool] = None) -> None:

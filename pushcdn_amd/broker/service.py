@@ -117,6 +117,14 @@ class BrokerConfig:
     # Off: each change is applied at once, per topic, with a DirectMap
     # rebuild per connect and disconnect, as before.
     gpu_batched_membership: bool = False
+    # what to do about a recipient whose egress ring overflowed on the GPU
+    # plane (its tick burst exceeded gpu_ring_bytes, or the tick the pair
+    # list): "ignore" drops the deliveries silently, as before; "count"
+    # turns the engine's loss accounting on and counts the lost bytes per
+    # recipient (metrics + one warning per lossy recipient per drain);
+    # "evict" also removes that user or broker once what did fit has been
+    # sent, the reference's send-or-remove (user/sender.rs).
+    gpu_overflow_policy: str = "ignore"
 
 
 @dataclass
@@ -140,11 +148,17 @@ class Broker:
     # through the collective path, which delivers inline records only, so
     # config.gpu_ref_threshold has no effect there
     REF_DELIVERY = True
+    # MeshBroker overrides to False: its collective tick drains on its own,
+    # so config.gpu_overflow_policy has no effect there
+    OVERFLOW_POLICY = True
 
     def __init__(self, config: BrokerConfig) -> None:
         from ..proto.transports.tcp import Tcp
 
         self.config = config
+        if config.gpu_overflow_policy not in ("ignore", "count", "evict"):
+            raise ValueError(f"gpu_overflow_policy {config.gpu_overflow_policy!r}: "
+                             "expected 'ignore', 'count' or 'evict'")
         config.public_advertise_endpoint = resolve_local_ip(config.public_advertise_endpoint)
         config.private_advertise_endpoint = resolve_local_ip(config.private_advertise_endpoint)
         self.identity = BrokerIdentifier(
@@ -173,6 +187,9 @@ class Broker:
         self._ref_threshold = (config.gpu_ref_threshold
                                if config.data_plane == "gpu" and type(self).REF_DELIVERY
                                else None)
+        self._overflow_policy = (config.gpu_overflow_policy
+                                 if config.data_plane == "gpu" and type(self).OVERFLOW_POLICY
+                                 else "ignore")
         if config.data_plane == "gpu":
             from .gpu_engine import GpuBrokerEngine
 
@@ -188,6 +205,7 @@ class Broker:
                 n_peer_slots=n_peer_slots,
                 fanout_wire=True,  # forward raw wire bytes verbatim
                 ref_threshold=self._ref_threshold,
+                loss_accounting=self._overflow_policy != "ignore",
                 # keyed routing hash: cluster-wide secret derived from the
                 # shared broker private key (see keyhash.derive_routing_seed)
                 hash_seed=derive_routing_seed(self.keypair.private_key),
@@ -925,6 +943,8 @@ class Broker:
         # must not hand this tick's bytes to its new occupant
         peers = [(broker, pslot, self.connections.brokers.get(broker))
                  for broker, pslot in self._peer_slot_of.items()]
+        overflowed = self._account_overflow(peers) \
+            if self._overflow_policy != "ignore" else []
         prev = self._last_drain
 
         async def _dispatch_chained():
@@ -934,10 +954,62 @@ class Broker:
                 except Exception:
                     pass
             await self._dispatch_egress(wpos, offsets, staging, peers, refbuf)
+            # after the delivered prefix went to the sockets: what fitted is
+            # still sent, as the reference sends everything before a failed send
+            if overflowed and self._overflow_policy == "evict":
+                await self._evict_overflowed(overflowed)
 
         task = asyncio.get_running_loop().create_task(_dispatch_chained())
         self._drain_by_buffer[idx] = task
         self._last_drain = task
+
+    def _account_overflow(self, peers):
+        """The recipients this drain found lossy (policies "count" and
+        "evict"): counters, one warning each, and who they are NOW, with the
+        drain — [(pubkey or BrokerIdentifier, handle)] — so that a slot
+        released and re-claimed before the eviction runs does not cost its
+        new occupant the connection.  A lossy slot nobody holds any more is
+        counted and otherwise dropped."""
+        from ..utils.metrics import GPU_RING_LOST_BYTES, GPU_RING_OVERFLOWS
+
+        losses = self._engine.take_losses()
+        if not losses:
+            return []
+        n_users = self._engine.n_users
+        peer_of = {pslot: (broker, handle) for broker, pslot, handle in peers}
+        overflowed = []
+        for r, lost in sorted(losses.items()):
+            GPU_RING_LOST_BYTES.inc(lost)
+            GPU_RING_OVERFLOWS.inc()
+            if r < n_users:
+                pubkey = self._gpu_user_by_slot.get(r)
+                handle = self.connections.users.get(pubkey) if pubkey is not None else None
+                who = ident(pubkey) if pubkey is not None else "nobody"
+                target = pubkey
+            else:
+                target, handle = peer_of.get(r - n_users, (None, None))
+                who = str(target) if target is not None else "nobody"
+            log.warning("egress ring overflow: recipient %d (%s) lost %d ring bytes",
+                        r, who, lost)
+            if target is not None and handle is not None:
+                overflowed.append((target, handle))
+        return overflowed
+
+    async def _evict_overflowed(self, overflowed) -> None:
+        from ..utils.metrics import GPU_RING_EVICTIONS
+
+        for target, handle in overflowed:
+            if isinstance(target, BrokerIdentifier):
+                if self.connections.brokers.get(target) is not handle:
+                    continue  # left or reconnected since the drain
+                log.warning("removing broker %s: egress ring overflow", target)
+                await self.remove_broker(target)
+            else:
+                if self.connections.users.get(target) is not handle:
+                    continue
+                log.warning("removing user %s: egress ring overflow", ident(target))
+                await self.remove_user(target)
+            GPU_RING_EVICTIONS.inc()
 
     async def _dispatch_egress(self, wpos, offsets, staging, peers=(),
                                refbuf=None) -> None:

@@ -64,6 +64,11 @@ def _broker_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--gpu-batched-membership", action="store_true",
                    help="GPU data plane: queue user joins, leaves and subscription "
                         "changes and apply them once per tick in one device batch")
+    p.add_argument("--gpu-overflow-policy", choices=["ignore", "count", "evict"],
+                   default="ignore",
+                   help="GPU data plane: what to do about a recipient whose egress ring "
+                        "overflowed: nothing (deliveries are dropped silently), count "
+                        "the lost bytes per recipient, or count and disconnect it")
     p.add_argument("--user-transport", choices=["tcp", "tcp-tls", "tcp-native", "quic", "quic-native"],
                    default="tcp", help="user-plane transport (tcp-native = C++ epoll "
                                        "pump; quic[-native] = QUIC-profile over UDP)")
@@ -89,6 +94,7 @@ def cmd_broker(args) -> None:
         gpu_device=args.gpu_device,
         gpu_ref_threshold=args.gpu_ref_threshold,
         gpu_batched_membership=args.gpu_batched_membership,
+        gpu_overflow_policy=args.gpu_overflow_policy,
         user_protocol=_transport(args.user_transport),
         broker_protocol=_transport(args.broker_transport),
     )

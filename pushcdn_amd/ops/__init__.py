@@ -55,3 +55,25 @@ def get_gpu_ctl_ops():
             pass
     _gpu_ctl_mod = build_gpu_ctl()
     return _gpu_ctl_mod
+
+
+_gpu_acct_mod = None
+
+
+def get_gpu_acct_ops():
+    """The loss-accounting extension (``pushcdn_gpu_acct``: K9
+    recipient_demand, K10 loss_scan), under the same rule as
+    ``get_gpu_ops()``."""
+    global _gpu_acct_mod
+    if _gpu_acct_mod is not None:
+        return _gpu_acct_mod
+    from .build import GPU_ACCT_BUILD_DIR, build_gpu_acct, load_gpu_acct_prebuilt
+
+    if (GPU_ACCT_BUILD_DIR / "pushcdn_gpu_acct.so").exists():
+        try:
+            _gpu_acct_mod = load_gpu_acct_prebuilt()
+            return _gpu_acct_mod
+        except ImportError:
+            pass
+    _gpu_acct_mod = build_gpu_acct()
+    return _gpu_acct_mod

@@ -1,10 +1,12 @@
 """In-tree build of the HIP/C++ extensions.
 
-Three modules:
+Four modules:
   - ``pushcdn_gpu``  — CDNA4 data-plane kernels (csrc/hip/*.hip) + torch bindings,
                        compiled for gfx950 only.
   - ``pushcdn_gpu_ctl`` — device-state maintenance kernels
                        (csrc/hip/membership.hip) + torch bindings, gfx950 only.
+  - ``pushcdn_gpu_acct`` — per-recipient loss-accounting kernels
+                       (csrc/hip/accounting.hip) + torch bindings, gfx950 only.
   - ``pushcdn_core`` — host C++ (wire serde, BLS-over-BN254, CRDT) via pybind11.
 
 Everything builds into ``<repo>/build/`` (in-tree, so the .so files travel to
@@ -35,6 +37,13 @@ GPU_CTL_BUILD_DIR = BUILD_DIR / "ctl"
 GPU_CTL_SOURCES = [
     CSRC / "gpu_ctl_bindings.cpp",
     CSRC / "hip" / "membership.hip",
+]
+
+# Likewise a directory of its own.
+GPU_ACCT_BUILD_DIR = BUILD_DIR / "acct"
+GPU_ACCT_SOURCES = [
+    CSRC / "gpu_acct_bindings.cpp",
+    CSRC / "hip" / "accounting.hip",
 ]
 
 os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
@@ -104,6 +113,17 @@ def build_gpu_ctl(verbose: bool = False):
 def load_gpu_ctl_prebuilt():
     """load_gpu_prebuilt for the maintenance extension."""
     return _load_prebuilt("pushcdn_gpu_ctl", GPU_CTL_BUILD_DIR / "pushcdn_gpu_ctl.so")
+
+
+def build_gpu_acct(verbose: bool = False):
+    """Compile (if needed) and load the loss-accounting extension
+    (K9 recipient_demand, K10 loss_scan). Returns the module."""
+    return _build_torch_ext("pushcdn_gpu_acct", GPU_ACCT_SOURCES, GPU_ACCT_BUILD_DIR, verbose)
+
+
+def load_gpu_acct_prebuilt():
+    """load_gpu_prebuilt for the loss-accounting extension."""
+    return _load_prebuilt("pushcdn_gpu_acct", GPU_ACCT_BUILD_DIR / "pushcdn_gpu_acct.so")
 
 
 CORE_SOURCES = [CSRC / "core_bindings.cpp"]

@@ -354,6 +354,57 @@ def membership_apply(
             ring_wpos[r] = 0
 
 
+def recipient_demand(
+    mask: torch.Tensor,         # int64 [M][W], origin clearing applied
+    ring_len: torch.Tensor,     # int32 [M], what K2b / K5b claim ring space from
+    disc: torch.Tensor,
+    owner: Optional[torch.Tensor],   # direct_lookup output; None = no Directs routed
+    origin,                     # [M] 0 = local; None = all local
+    n_users: int,
+    n_peers: int,
+    demand: torch.Tensor,       # int64 [n_users + n_peers], mutated
+) -> None:
+    """Mirror of k9_recipient_demand (mask untransposed, [M][W]):
+    demand[r] += ring_rec(ring_len[m]) for every message m of the tick that
+    addresses recipient r — a Broadcast through bit r of its mask row, a
+    Direct through the recipient emit_direct_peers resolves (which see).
+    Whether the delivery then fits the ring plays no part."""
+    M = int(ring_len.shape[0])
+    R = n_users + n_peers
+    add = [0] * R
+    for m in range(M):
+        rec = ring_rec(int(ring_len[m]))
+        for w, word in enumerate(mask[m].tolist()):
+            word &= (1 << 64) - 1
+            while word:
+                low = word & -word
+                r = w * 64 + low.bit_length() - 1
+                if r < R:
+                    add[r] += rec
+                word ^= low
+        if owner is None or int(disc[m]) != 3:
+            continue
+        o = int(owner[m])
+        if o >= 0:
+            if o < n_users:
+                add[o] += rec
+        else:
+            p = -o - 2
+            if 0 <= p < n_peers and (origin is None or int(origin[m]) == 0):
+                add[n_users + p] += rec
+    demand += torch.tensor(add, dtype=torch.int64)
+
+
+def loss_scan(demand: torch.Tensor, ring_wpos: torch.Tensor) -> List[Tuple[int, int]]:
+    """Mirror of k10_loss_scan: [(r, demand[r] - ring_wpos[r])] over the
+    recipients where the two differ, in recipient order (the kernel's order
+    is unspecified); demand is zeroed, ring_wpos only read."""
+    out = [(r, int(d) - int(w))
+           for r, (d, w) in enumerate(zip(demand.tolist(), ring_wpos.tolist())) if d != w]
+    demand.zero_()
+    return out
+
+
 def compact_rings(egress: bytes, ring_bytes: int, wpos) -> Tuple[List[int], bytes]:
     """Mirror of k7_compact_rings: every ring's used prefix, concatenated in
     ring order.  Returns (offsets, staging bytes); offsets is the exclusive

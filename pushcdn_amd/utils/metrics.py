@@ -129,6 +129,13 @@ BYTES_RECV = _counter("total_bytes_recv", "Total bytes received over all connect
 LATENCY = _LatencyHistogram("latency", "In-broker message allocation lifetime (s)")
 NUM_USERS_CONNECTED = _gauge("num_users_connected", "Users connected to this broker")
 NUM_BROKERS_CONNECTED = _gauge("num_brokers_connected", "Brokers connected to this broker")
+# GPU data plane with gpu_overflow_policy "count" or "evict"
+GPU_RING_LOST_BYTES = _counter(
+    "gpu_ring_lost_bytes", "Egress ring bytes dropped on the device for want of ring space")
+GPU_RING_OVERFLOWS = _counter(
+    "gpu_ring_overflows", "Recipients that lost egress ring bytes, counted per drain")
+GPU_RING_EVICTIONS = _counter(
+    "gpu_ring_evictions", "Users and brokers removed after an egress ring overflow")
 
 
 def render_metrics() -> bytes:
