@@ -36,6 +36,13 @@ static inline int64_t dense_grid_x(int32_t n_users, int32_t group, int32_t n_chu
     return ((int64_t)n_users + group - 1) / group * n_chunks;
 }
 
+// Flat fan-out workgroups (256 threads each) that follow the dense ones in the
+// fused tick's fan-out launch and walk the sparse list.  16,384 is the grid
+// swept for the flat kernel where the list carries the whole fan-out
+// (16384 > 8192 > 4096, about 0.5% each), which a population with no dense
+// tile still is.
+#define SPARSE_TAIL_BLOCKS 16384
+
 // Elements of the two scratch tensors the fused tick carves its per-tick
 // arrays from, for a batch of M messages and W mask words (NB = blocks of
 // K2B_BLK messages, U = W * 64 user slots):

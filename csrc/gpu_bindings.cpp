@@ -625,10 +625,11 @@ void tick_uniform_broadcast(torch::Tensor buf, torch::Tensor offsets, uint64_t h
     TORCH_CHECK(buf.numel() >= M * uniform_len, a.name(), ": buf has ", buf.numel(),
                 " bytes, shorter than M = ", M, " messages of uniform_len = ", uniform_len);
     check_flat_shape(pairs, rec / 16);
-    // the image kernel's unit index and the dense fan-out's 1-D grid
+    // the image kernel's unit index and the fan-out's 1-D grid: the dense
+    // workgroups and the sparse tail behind them
     TORCH_CHECK(M * (rec / 16) < (int64_t(1) << 31)
                 && dense_grid_x(t.n_users, DENSE_GROUP, dense_geom((int32_t)(rec / 16)).n_chunks)
-                       * k2b_blocks(M) < (int64_t(1) << 31),
+                       * k2b_blocks(M) + SPARSE_TAIL_BLOCKS < (int64_t(1) << 31),
                 a.name(), ": batch too large for the dense fan-out");
     TORCH_CHECK((uintptr_t)t.scratch64 % 16 == 0, a.name(), ": scratch64 must be 16-byte aligned");
     hipStream_t s = a.begin();
@@ -641,9 +642,13 @@ std::vector<int64_t> uniform_tick_scratch_sizes(int64_t M, int64_t W, int64_t re
     return {uniform_tick_scratch64(M, W, rec / 16), uniform_tick_scratch32(M, W)};
 }
 
-// Fused drain: one kernel copies the cursors to `staging` and zeroes them,
-// one async copy lands them in the engine's pinned `host` buffer, one stream
-// synchronise makes that buffer readable.
+// Fused drain: one kernel stores the cursors into the engine's pinned `host`
+// buffer, through that buffer's device-visible address, and zeroes them; one
+// stream synchronise makes the buffer readable.  A pinned buffer without a
+// device-visible address takes two hops: the kernel stores to `staging` and
+// an async copy lands that in `host`.  Pinned memory always has such an
+// address on the hardware this is built for, so no GPU test reaches the two
+// hops; they are the path this op took before it stored directly.
 void drain_cursors(torch::Tensor ring_wpos, torch::Tensor staging, torch::Tensor host) {
     Op a("drain_cursors");
     int64_t* wpos = a.ptr<int64_t>(ring_wpos, "ring_wpos");
@@ -652,15 +657,24 @@ void drain_cursors(torch::Tensor ring_wpos, torch::Tensor staging, torch::Tensor
     int64_t* h = a.ptr<int64_t>(host, "host", n, {}, Op::kPinnedHost);
     hipStream_t s = a.begin();
     if (n == 0) return;
-    launch_drain_cursors(wpos, st, n, s);
-    a.launched();
-    a.check(hipMemcpyAsync(h, st, (size_t)n * 8, hipMemcpyDeviceToHost, s), "copy");
+    void* h_dev = nullptr;
+    if (hipHostGetDevicePointer(&h_dev, h, 0) == hipSuccess && h_dev != nullptr) {
+        launch_drain_cursors(wpos, (int64_t*)h_dev, n, s);
+        a.launched();
+    } else {
+        (void)hipGetLastError();  // clear it: the two hops below need no device view
+        launch_drain_cursors(wpos, st, n, s);
+        a.launched();
+        a.check(hipMemcpyAsync(h, st, (size_t)n * 8, hipMemcpyDeviceToHost, s), "copy");
+    }
     a.check(hipStreamSynchronize(s), "sync");
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     // largest batch tick_uniform_broadcast routes in one kernel (tick_geom.h)
     m.attr("_ROUTE_MAX_M") = py::int_(ROUTE_MAX_M);
+    // flat workgroups behind the dense ones in its fan-out launch (tick_geom.h)
+    m.attr("_SPARSE_TAIL_BLOCKS") = py::int_(SPARSE_TAIL_BLOCKS);
     m.def("tick_uniform_broadcast", &tick_uniform_broadcast,
           "fused uniform broadcast tick: K4, K2a, K2b tiles, dense + sparse fan-out");
     m.def("uniform_tick_scratch_sizes", &uniform_tick_scratch_sizes,

@@ -144,11 +144,13 @@ void launch_k6_direct_apply(uint64_t* table_keys, int32_t* table_vals, int64_t t
                             hipStream_t s);
 
 // Fused uniform broadcast tick: K4, K2a, K2b (tiles), the dense fan-out and
-// the flat fan-out over the sparse list, back to back on one stream.
+// the flat fan-out over the sparse list (one launch for the two), back to back
+// on one stream.
 void launch_tick_uniform_broadcast(const UniformTick* t, hipStream_t s);
 
-// Drain: staging[i] = ring_wpos[i]; ring_wpos[i] = 0
-void launch_drain_cursors(int64_t* ring_wpos, int64_t* staging, int32_t n, hipStream_t s);
+// Drain: out[i] = ring_wpos[i]; ring_wpos[i] = 0.  `out` is any address the
+// device can store to: a device buffer or the device view of pinned host memory.
+void launch_drain_cursors(int64_t* ring_wpos, int64_t* out, int32_t n, hipStream_t s);
 
 // K7
 void launch_k7_compact_rings(const uint8_t* egress, int64_t ring_bytes, const int64_t* wpos,

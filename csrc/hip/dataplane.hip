@@ -48,16 +48,17 @@
 //   K7  k7_compact_rings — gather used ring prefixes into one staging buffer
 //   fused uniform broadcast tick (launch_tick_uniform_broadcast, end of this
 //                        file) — the broadcast-only uniform shape as one
-//                        launcher call of four launches: k_tick_prologue (K4,
+//                        launcher call of three launches: k_tick_prologue (K4,
 //                        the dense fan-out's record image, counters zeroed),
 //                        k_route_word (K2a, P1, P2 plus a dense / sparse sort
 //                        of the (user, block) tiles, and pairs for the sparse
-//                        tiles only, one mask word per workgroup, in LDS),
-//                        k3_fanout_dense (dense tiles stored from registers,
-//                        no pair records) and the flat K3 over the sparse
-//                        list.  Above ROUTE_MAX_M messages k2a_topic_mask_t,
-//                        k2b_p1_count_z, k2b_p2_tiles and k2b_p3_sparse route
-//                        through scratch.  k_drain_cursors is the fused drain
+//                        tiles only, one mask word per workgroup, in LDS) and
+//                        k3_fanout_dense_tail_t (dense tiles stored from
+//                        registers, no pair records, and behind them the flat
+//                        K3 over the sparse list).  Above ROUTE_MAX_M messages
+//                        k2a_topic_mask_t, k2b_p1_count_z, k2b_p2_tiles and
+//                        k2b_p3_sparse route through scratch.
+//                        k_drain_cursors is the fused drain
 //
 // Shared device building blocks, each defined once and force-inlined:
 //   store16<NT>        the only place the non-temporal store choice is made
@@ -70,6 +71,8 @@
 //                      k2b_fused_t, k2b_p2_bases
 //   k4_parse_body      one message's parse — k4_parse_batch, k_tick_prologue
 //   k3d_image_body     one unit of the record image — k_tick_prologue
+//   k3_flat_body       one workgroup of the flat fan-out — k3_fanout_flat_t,
+//                      k3_fanout_dense_tail_t
 //   k2b_tile_count, k2b_p2_body, k2b_tiles_body, k2b_p3_sparse_body
 //                      P1, P2, the tile sort and P3 over tiles in scratch or
 //                      in LDS — the k2b_p* kernels and k_route_word
@@ -834,14 +837,17 @@ __device__ __forceinline__ cdn_v4u payload_unit(const uint8_t* __restrict__ msg,
     return v;
 }
 
-template <int NT, bool SEQ_FROM_PTR>
-__global__ void __launch_bounds__(256) k3_fanout_flat_t(
+// The flat fan-out as workgroup `block` of `n_blocks`: the count read and
+// clamped, then a grid-stride walk over the list's units.  The one definition
+// of that walk: k3_fanout_flat_t is a grid of these, and the fused tick's
+// k3_fanout_dense_tail_t runs them behind its dense workgroups.
+template <int NT>
+__device__ __forceinline__ void k3_flat_body(
     const uint8_t* __restrict__ buf,
     const int64_t* __restrict__ payload_off,
     const int32_t* __restrict__ payload_len,
     const PairRec* __restrict__ pairs,
-    uint32_t seq_base_val,
-    const uint32_t* __restrict__ seq_state,
+    uint32_t seq_base,
     const int32_t* __restrict__ n_pairs_ptr,
     int32_t capacity,
     int32_t units_per_pair,
@@ -851,14 +857,14 @@ __global__ void __launch_bounds__(256) k3_fanout_flat_t(
                                           // ~25 VALU ops on the hottest loop)
     int32_t uniform_len,                  // >0: every record is this long —
                                           // skips the per-unit length load
-    uint8_t* __restrict__ egress)
+    uint8_t* __restrict__ egress,
+    uint32_t block, uint32_t n_blocks)
 {
-    const uint32_t seq_base = SEQ_FROM_PTR ? seq_state[0] : seq_base_val;
     int np = *n_pairs_ptr;
     if (np > capacity) np = capacity;
     const int64_t n_units = (int64_t)np * units_per_pair;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < n_units; f += stride) {
+    const int64_t stride = (int64_t)n_blocks * blockDim.x;
+    for (int64_t f = (int64_t)block * blockDim.x + threadIdx.x; f < n_units; f += stride) {
         const uint32_t f32 = (uint32_t)f;  // n_units < 2^31 (capacity*units)
         const int p = (int)(((uint64_t)f32 * div_magic) >> div_shift);
         const int unit = (int)(f32 - (uint32_t)p * (uint32_t)units_per_pair);
@@ -873,6 +879,27 @@ __global__ void __launch_bounds__(256) k3_fanout_flat_t(
         }
         store16<NT>(dst, payload_unit(buf + payload_off[mi], (unit - 1) * 16, len));
     }
+}
+
+template <int NT, bool SEQ_FROM_PTR>
+__global__ void __launch_bounds__(256) k3_fanout_flat_t(
+    const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ payload_off,
+    const int32_t* __restrict__ payload_len,
+    const PairRec* __restrict__ pairs,
+    uint32_t seq_base_val,
+    const uint32_t* __restrict__ seq_state,
+    const int32_t* __restrict__ n_pairs_ptr,
+    int32_t capacity,
+    int32_t units_per_pair,
+    uint32_t div_magic, int32_t div_shift,
+    int32_t uniform_len,
+    uint8_t* __restrict__ egress)
+{
+    const uint32_t seq_base = SEQ_FROM_PTR ? seq_state[0] : seq_base_val;
+    k3_flat_body<NT>(buf, payload_off, payload_len, pairs, seq_base, n_pairs_ptr, capacity,
+                     units_per_pair, div_magic, div_shift, uniform_len, egress, blockIdx.x,
+                     gridDim.x);
 }
 
 // u32_div_magic (csrc/common/divmagic.h): p = (f * m) >> sh, exact for all
@@ -1546,8 +1573,9 @@ void launch_k6_direct_apply(uint64_t* table_keys, int32_t* table_vals, int64_t t
 //                     sort of each (user, 32-message block) TILE into dense
 //                     or sparse, and P3's pair records for the sparse tiles
 //                     only; one workgroup per mask word, tiles in LDS
-//   K3d k3_fanout_dense    the dense tiles, from registers
-//   K3  k3_fanout_flat_t   the sparse list (flat2, as on the per-op path)
+//   k3_fanout_dense_tail_t  one launch of two kinds of workgroup:
+//     K3d k3_dense_body    the dense tiles, from registers
+//     K3  k3_flat_body     the sparse list (flat2, as on the per-op path)
 //
 // Two launches stand ahead of the dense fan-out because the step starts on
 // an empty queue and every launch ahead of it is host time the GPU waits
@@ -1846,15 +1874,15 @@ extern "C" __global__ void __launch_bounds__(256) k_tick_prologue(
 // nt_fanout setting: on the bench's layout this shape measured 510 us plain
 // against 540 us non-temporal (profiles/k3_write_shapes.txt), the opposite
 // of the flat kernel.
-__global__ void __launch_bounds__(DENSE_THREADS) k3_fanout_dense(
+__device__ __forceinline__ void k3_dense_body(
     const cdn_v4u* __restrict__ image,     // [M * units_per_rec]
     const int64_t* __restrict__ tdst,      // [NB][users64]
     int32_t M, int32_t NB, int32_t users64, int32_t n_users, int32_t units_per_rec,
     int32_t n_chunks, int32_t chunk_units, int32_t group,
-    uint8_t* __restrict__ egress)
+    uint8_t* __restrict__ egress, uint32_t block)
 {
     const int per_group = NB * n_chunks;
-    const int g = blockIdx.x / per_group, bc = blockIdx.x - g * per_group;
+    const int g = block / per_group, bc = block - g * per_group;
     const int b = bc / n_chunks, c = bc - b * n_chunks;
     const int m0 = b * K2B_BLK, nm = min(M - m0, K2B_BLK);
     const int lo = c * chunk_units + (int)threadIdx.x;
@@ -1880,12 +1908,48 @@ __global__ void __launch_bounds__(DENSE_THREADS) k3_fanout_dense(
     }
 }
 
+// The fused tick's one fan-out launch.  Workgroups [0, dense_blocks) are K3d;
+// the SPARSE_TAIL_BLOCKS behind them are the flat K3 over the sparse list
+// (pairs[0 .. *n_sparse), offsets as payload_off, the length a scalar), with
+// the stores NT chooses.  The two halves write disjoint ring spans, both
+// handed out by the routing launch before this one, so nothing orders them
+// and no workgroup waits for another.  The tail is dispatched behind the
+// dense workgroups: with an empty list it reads the count and is gone while
+// the last of them still store, where a launch of its own stood between the
+// fan-out and the drain.
+static_assert(DENSE_THREADS == 256, "the tail runs the flat body, 256 threads per workgroup");
+template <int NT>
+__global__ void __launch_bounds__(DENSE_THREADS) k3_fanout_dense_tail_t(
+    const cdn_v4u* __restrict__ image,
+    const int64_t* __restrict__ tdst,
+    int32_t M, int32_t NB, int32_t users64, int32_t n_users, int32_t units_per_rec,
+    int32_t n_chunks, int32_t chunk_units, int32_t group, uint32_t dense_blocks,
+    const uint8_t* __restrict__ buf,
+    const int64_t* __restrict__ offsets,
+    const int32_t* __restrict__ payload_len,
+    const PairRec* __restrict__ pairs,
+    uint32_t seq_base,
+    const int32_t* __restrict__ n_sparse,
+    int32_t capacity, uint32_t div_magic, int32_t div_shift, int32_t uniform_len,
+    uint8_t* __restrict__ egress)
+{
+    if (blockIdx.x < dense_blocks)
+        k3_dense_body(image, tdst, M, NB, users64, n_users, units_per_rec, n_chunks, chunk_units,
+                      group, egress, blockIdx.x);
+    else
+        k3_flat_body<NT>(buf, offsets, payload_len, pairs, seq_base, n_sparse, capacity,
+                         units_per_rec, div_magic, div_shift, uniform_len, egress,
+                         blockIdx.x - dense_blocks, gridDim.x - dense_blocks);
+}
+
+// `out` is the device-visible address of the engine's pinned host buffer, or
+// a device staging buffer where the host buffer has none.
 extern "C" __global__ void k_drain_cursors(int64_t* __restrict__ ring_wpos,
-                                           int64_t* __restrict__ staging, int32_t n)
+                                           int64_t* __restrict__ out, int32_t n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    staging[i] = ring_wpos[i];
+    out[i] = ring_wpos[i];
     ring_wpos[i] = 0;
 }
 
@@ -1954,23 +2018,30 @@ void launch_tick_uniform_broadcast(const UniformTick* t, hipStream_t s) {
                            t->pairs);
     }
 
-    // 3. the fan-out
+    // 3. the fan-out: one launch, the sparse list behind the dense tiles; the
+    // flat kernel alone with the dense fan-out off.  offsets is payload_off
+    // (fanout_wire), the length a scalar.
     if (t->dense) {
         const DenseGeom geo = dense_geom(units);
-        const dim3 grid((uint32_t)(dense_grid_x(t->n_users, DENSE_GROUP, geo.n_chunks) * NB));
-        hipLaunchKernelGGL(k3_fanout_dense, grid, dim3(DENSE_THREADS), 0, s, image, tdst, M, NB,
-                           (int32_t)U, t->n_users, units, geo.n_chunks, geo.chunk_units,
-                           DENSE_GROUP, t->egress);
+        const uint32_t dense_blocks =
+            (uint32_t)(dense_grid_x(t->n_users, DENSE_GROUP, geo.n_chunks) * NB);
+        DISPATCH_NT(t->nt, hipLaunchKernelGGL(
+            (k3_fanout_dense_tail_t<NT>), dim3(dense_blocks + SPARSE_TAIL_BLOCKS),
+            dim3(DENSE_THREADS), 0, s, image, tdst, M, NB, (int32_t)U, t->n_users, units,
+            geo.n_chunks, geo.chunk_units, DENSE_GROUP, dense_blocks, t->buf, t->offsets,
+            payload_len, t->pairs, t->seq_base, t->n_sparse, t->capacity, dm, dsh,
+            t->uniform_len, t->egress));
+    } else {
+        launch_flat<false>(t->buf, t->offsets, payload_len, t->pairs, t->seq_base, nullptr,
+                           t->n_sparse, t->capacity, units, t->uniform_len, t->egress, t->nt, 0,
+                           s);
     }
-    // the sparse list: offsets is payload_off (fanout_wire), the length a scalar
-    launch_flat<false>(t->buf, t->offsets, payload_len, t->pairs, t->seq_base, nullptr,
-                       t->n_sparse, t->capacity, units, t->uniform_len, t->egress, t->nt, 0, s);
 }
 
-void launch_drain_cursors(int64_t* ring_wpos, int64_t* staging, int32_t n, hipStream_t s) {
+void launch_drain_cursors(int64_t* ring_wpos, int64_t* out, int32_t n, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_drain_cursors, dim3((n + 255) / 256), dim3(256), 0, s, ring_wpos,
-                       staging, n);
+    hipLaunchKernelGGL(k_drain_cursors, dim3((n + 255) / 256), dim3(256), 0, s, ring_wpos, out,
+                       n);
 }
 
 }  // extern "C"

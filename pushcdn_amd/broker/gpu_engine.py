@@ -223,6 +223,7 @@ class GpuBrokerEngine:
             self._n_sparse = torch.zeros(1, **o32)
             self._dense_fanout = True
             self._fused_scratch = None
+            self._fused_scratch_shape = None  # (M, W, wire length) it was last sized for
             self._drain_bufs = None
             self._graphs: Dict[Tuple[int, int, int], object] = {}
 
@@ -740,15 +741,19 @@ class GpuBrokerEngine:
     def _tick_fused(self, buf: torch.Tensor, offsets: torch.Tensor,
                     uniform_wire_len: int, M: int) -> TickStats:
         ops = self._ops
-        # engine-owned scratch, grown to the largest shape seen so far
-        n64, n32 = ops.uniform_tick_scratch_sizes(M, self.W, ring_rec(uniform_wire_len))
+        # engine-owned scratch, grown to the largest shape seen so far; a
+        # shape that repeats needs no second look at its sizes
+        shape = (M, self.W, uniform_wire_len)
         s64, s32 = self._fused_scratch or (None, None)
-        if s64 is None or s64.numel() < n64 or s32.numel() < n32:
-            s64 = torch.empty(max(n64, 0 if s64 is None else s64.numel()),
-                              dtype=torch.int64, device=self.device)
-            s32 = torch.empty(max(n32, 0 if s32 is None else s32.numel()),
-                              dtype=torch.int32, device=self.device)
-            self._fused_scratch = (s64, s32)
+        if shape != self._fused_scratch_shape:
+            n64, n32 = ops.uniform_tick_scratch_sizes(M, self.W, ring_rec(uniform_wire_len))
+            if s64 is None or s64.numel() < n64 or s32.numel() < n32:
+                s64 = torch.empty(max(n64, 0 if s64 is None else s64.numel()),
+                                  dtype=torch.int64, device=self.device)
+                s32 = torch.empty(max(n32, 0 if s32 is None else s32.numel()),
+                                  dtype=torch.int32, device=self.device)
+                self._fused_scratch = (s64, s32)
+            self._fused_scratch_shape = shape
         seq_base = self.seq
         self.seq += M
         ops.tick_uniform_broadcast(

@@ -12,7 +12,9 @@ timeline table: per kernel, the median duration and the median IDLE time
 before it, i.e. from the end of the dispatch that finished last before it
 to its own start.  With --interval KERNEL it also gives the median interval
 from the end of one KERNEL dispatch to the start of the next, and how much
-of that interval other kernels were running.
+of that interval other kernels were running, KERNEL's own shortest, median
+and longest dispatch, and the dispatches that stand between two KERNELs one
+by one, in order, each with its median duration and idle time before it.
 """
 
 import csv
@@ -109,7 +111,9 @@ def timeline_text(interval_kernel):
         lines.append(f"{nm[:52]:<52} {len(dur[nm]):>6} {median(dur[nm]):>11.2f} "
                      f"{median(idle.get(nm, [])):>19.2f}")
     if interval_kernel:
-        marks = [i for i, (_s, _e, nm) in enumerate(tl) if nm.startswith(interval_kernel)]
+        # a template instance's name starts with its return type
+        marks = [i for i, (_s, _e, nm) in enumerate(tl)
+                 if nm.removeprefix("void ").startswith(interval_kernel)]
         spans, busy = [], []
         for a, b in zip(marks, marks[1:]):
             spans.append((tl[b][0] - tl[a][1]) / 1e3)
@@ -120,7 +124,36 @@ def timeline_text(interval_kernel):
                       f"{len(spans)} intervals: {median(spans):.1f} us, "
                       f"kernel time inside it {median(busy):.1f} us, "
                       f"idle {median(spans) - median(busy):.1f} us"]
+        if marks:
+            lines += chain_lines(tl, marks, interval_kernel)
     return "\n".join(lines) + "\n"
+
+
+def chain_lines(tl, marks, interval_kernel):
+    """KERNEL's own durations, and the dispatches between one KERNEL and the
+    next, position by position: a name shared by several launches of a step
+    (the blit kernel of every copy) is told apart by where it stands."""
+    durs = [(tl[i][1] - tl[i][0]) / 1e3 for i in marks]
+    lines = ["", f"{interval_kernel}: {len(durs)} dispatches, duration min {min(durs):.2f} / "
+                 f"median {median(durs):.2f} / max {max(durs):.2f} us, "
+                 f"spread {max(durs) - min(durs):.2f} us"]
+    pairs = list(zip(marks, marks[1:]))
+    pairs = pairs[len(pairs) // 2:]  # the steady state, as above
+    chains = {}
+    for a, b in pairs:
+        chains.setdefault(tuple(nm for _s, _e, nm in tl[a + 1:b]), []).append(a)
+    if not chains:
+        return lines
+    names, starts = max(chains.items(), key=lambda kv: len(kv[1]))
+    lines += ["", f"dispatches after {interval_kernel} up to the next one, in order "
+                  f"({len(starts)} of the last {len(pairs)} intervals have this sequence):",
+              f"{'#':>2} {'kernel':<52} {'med_dur_us':>11} {'med_idle_before_us':>19}"]
+    for k, nm in enumerate(names):
+        d = [(tl[a + 1 + k][1] - tl[a + 1 + k][0]) / 1e3 for a in starts]
+        idle = [max(0, tl[a + 1 + k][0] - max(e for _s, e, _n in tl[:a + 1 + k])) / 1e3
+                for a in starts]
+        lines.append(f"{k + 1:>2} {nm[:52]:<52} {median(d):>11.2f} {median(idle):>19.2f}")
+    return lines
 
 
 def extract_csv(path):
