@@ -46,23 +46,35 @@ import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
-from ..utils.keyhash import fnv1a64
-from ..utils.log import get_logger
-
-log = get_logger("gpu-engine")
-
-RING_ALIGN = 16
-REF_FLAG = 0x80000000  # top bit of a record's len word: by-reference record
+from ..ops import reference as ref
+# the ring record format is re-exported: callers import it from here
+from ..ops.ring_format import RING_ALIGN, REF_FLAG, parse_ring_records, ring_rec  # noqa: F401
+from ..utils.keyhash import as_i64
+from .direct_map import DirectMap
 
 
-def ring_rec(length: int) -> int:
-    """Egress ring record stride: 16 B header + payload padded to 16 B
-    (uint4-aligned record starts).  Host mirror of csrc/hip/dataplane.hip
-    ring_rec; K3 zero-pads the tail unit so each record is written with
-    full vector stores."""
-    return (length + 16 + (RING_ALIGN - 1)) & ~(RING_ALIGN - 1)
+def _k6_apply(ops, device):
+    """The DirectMap's incremental device update on the GPU plane, as the
+    callable DirectMap takes: one K6 launch per call."""
+    n_failed = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def apply(keys, vals, up_list, dels) -> int:
+        up_keys = torch.tensor([as_i64(h) for h, _ in up_list], dtype=torch.int64).to(device)
+        up_owners = torch.tensor([o for _, o in up_list], dtype=torch.int32).to(device)
+        del_keys = torch.tensor([as_i64(h) for h in dels], dtype=torch.int64).to(device)
+        ops.direct_apply(keys, vals, up_keys, up_owners, del_keys, n_failed)
+        # A 4-byte readback, also on a tick whose membership flush carries
+        # DirectMap changes: an insert that found no slot has to be repaired
+        # by a rebuild BEFORE that tick's K5 looks the key up.
+        failed = int(n_failed.cpu()[0])
+        if failed:
+            n_failed.zero_()
+        return failed
+
+    return apply
 
 
 @dataclass
@@ -156,19 +168,17 @@ class GpuBrokerEngine:
         self.sub_bitmap = torch.zeros((256, self.W), dtype=torch.int64, device=dev)
         self.egress = torch.zeros(R * ring_bytes, dtype=torch.uint8, device=dev)
         self.ring_wpos = torch.zeros(R, dtype=torch.int64, device=dev)
-        self.direct_keys = torch.zeros(direct_table_size, dtype=torch.int64, device=dev)
-        self.direct_vals = torch.zeros(direct_table_size, dtype=torch.int32, device=dev)
-        self._direct_entries: Dict[int, int] = {}
-        self._direct_pubkeys: Dict[int, bytes] = {}  # hash -> full key (collision refusal)
-        # hashes whose key still sits in the device table with a tombstoned
-        # value (apply_direct_updates deletes); cleared by every rebuild
-        self._direct_tombstones: set = set()
-        self._direct_failed = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the DirectMap (device table + host mirror); the CPU model is looked
+        # up per call
+        self.directs = DirectMap(
+            direct_table_size, dev, self.hash_seed,
+            _k6_apply(self._ops, dev) if self.use_gpu_ops
+            else lambda *args: ref.direct_apply(*args))
+        self.direct_keys = self.directs.keys
+        self.direct_vals = self.directs.vals
         # the membership log (see queue_join): recipient -> [clear, set, reset]
-        # with 256-bit topic sets as ints, and routing hash -> (owner or None
-        # for a delete, whether the device table held the hash beforehand)
+        # with 256-bit topic sets as ints; its DirectMap half is directs.pending
         self._mship_rows: Dict[int, list] = {}
-        self._mship_direct: Dict[int, Tuple[Optional[int], bool]] = {}
         self._ctl_ops = None  # pushcdn_gpu_ctl, loaded by the first flush
         # by-reference delivery (None = off: exactly the inline kernels).
         # Needs fanout_wire, so that host and device both know a message's
@@ -208,8 +218,12 @@ class GpuBrokerEngine:
                                                  pin_memory=self.is_cuda)
         self.seq = 0
         self.total = TickStats()
+        # drain_compact's device staging and its two pinned host buffers;
+        # _staging_flip is the host buffer the next drain fills
         self._staging_dev: Optional[torch.Tensor] = None
-        self._staging_host: Optional[torch.Tensor] = None
+        self._staging_host: Optional[List[torch.Tensor]] = None
+        self._staging_flip = 0
+        self._k2b_scratch = None  # (blocks it serves, block-K2b buffers)
         if self.use_gpu_ops:
             o32 = dict(dtype=torch.int32, device=dev)
             # delivery pairs as 16 B AoS records {i32 user, i32 msg, i64 dst}
@@ -229,17 +243,20 @@ class GpuBrokerEngine:
 
     # ---------------- subscription management (host-driven) ----------------
 
+    @staticmethod
+    def _word_bit(recipient: int) -> Tuple[int, int]:
+        """Bitmap word index and (int64) bit of a recipient."""
+        return recipient >> 6, as_i64(1 << (recipient & 63))
+
     def subscribe(self, user_idx: int, topics: List[int]) -> None:
         self.flush_membership()
-        w, bit = user_idx >> 6, 1 << (user_idx & 63)
-        bit = bit - (1 << 64) if bit >= (1 << 63) else bit
+        w, bit = self._word_bit(user_idx)
         for t in topics:
             self.sub_bitmap[t & 0xFF, w] |= bit
 
     def unsubscribe(self, user_idx: int, topics: List[int]) -> None:
         self.flush_membership()
-        w, bit = user_idx >> 6, 1 << (user_idx & 63)
-        bit = bit - (1 << 64) if bit >= (1 << 63) else bit
+        w, bit = self._word_bit(user_idx)
         for t in topics:
             self.sub_bitmap[t & 0xFF, w] &= ~bit
 
@@ -275,9 +292,7 @@ class GpuBrokerEngine:
     def _peer_word_bit(self, p: int) -> Tuple[int, int]:
         if not 0 <= p < self.n_peer_slots:
             raise IndexError(f"peer slot {p} outside [0, {self.n_peer_slots})")
-        r = self.n_users + p
-        bit = 1 << (r & 63)
-        return r >> 6, (bit - (1 << 64) if bit >= (1 << 63) else bit)
+        return self._word_bit(self.n_users + p)
 
     def set_peer_topics(self, p: int, topics: List[int]) -> None:
         """Make `topics` the exact interest set of peer slot p: a local
@@ -303,50 +318,30 @@ class GpuBrokerEngine:
             # must not inherit a loss
             self.demand[self.n_users + p] = 0
 
-    def _direct_hash(self, pubkey: bytes) -> int:
-        """Routing hash of a pubkey, with collision refusal: if a DIFFERENT
-        pubkey already registered the same 64-bit hash, registering this one
-        would silently misroute one user's Direct traffic to the other —
-        refuse instead (accidental probability 2^-64/pair; adversarial
-        construction requires the secret seed)."""
-        h = fnv1a64(pubkey, self.hash_seed)
-        prev = self._direct_pubkeys.get(h)
-        if prev is not None and prev != pubkey:
-            raise ValueError("direct routing-hash collision; refusing registration")
-        return h
-
     def register_direct(self, pubkey: bytes, owner: int) -> None:
-        """owner >= 0: local user index. owner <= -2: peer slot -(p+2)."""
+        """owner >= 0: local user index. owner <= -2: peer slot -(p+2).
+        Raises ValueError on a routing-hash collision with a different
+        registered key (or routing hash 0) and RuntimeError("direct table
+        full"); a refusal changes nothing."""
         self.flush_membership()
-        h = self._direct_hash(pubkey)
-        self._direct_pubkeys[h] = pubkey
-        self._direct_entries[h] = owner
-        self._rebuild_direct_table()
+        self.directs.register([(pubkey, owner)])
 
     def register_direct_bulk(self, entries) -> None:
-        """Register many (pubkey, owner) pairs with one table rebuild."""
+        """Register many (pubkey, owner) pairs with one table rebuild, or
+        none of them if one is refused."""
         self.flush_membership()
-        for pubkey, owner in entries:
-            h = self._direct_hash(pubkey)
-            self._direct_pubkeys[h] = pubkey
-            self._direct_entries[h] = owner
-        self._rebuild_direct_table()
+        self.directs.register(entries)
 
     def unregister_direct(self, pubkey: bytes) -> None:
         """Remove a departed user's entry so a Direct to their key is dropped
         instead of delivered to whoever reuses the slot."""
         self.flush_membership()
-        h = fnv1a64(pubkey, self.hash_seed)
-        if self._direct_entries.pop(h, None) is not None:
-            self._direct_pubkeys.pop(h, None)
-            self._rebuild_direct_table()
+        self.directs.unregister(pubkey)
 
     def subscribe_modulo(self, n_topics: int) -> None:
         """Bulk: user u subscribes to topic (u % n_topics) — the mixed-bench
         population shape. Vectorized bitmap build on host, one H2D copy."""
         self.flush_membership()
-        import numpy as np
-
         bitmap = np.zeros((256, self.W), dtype=np.uint64)
         users = np.arange(self.n_users)
         for t in range(n_topics):
@@ -361,20 +356,9 @@ class GpuBrokerEngine:
             new |= self.sub_bitmap & ~self._user_bit_words().to(self.device)
         self.sub_bitmap.copy_(new)
 
-    def _rebuild_direct_table(self) -> None:
-        from ..ops.reference import build_direct_table
-
-        keys, vals = build_direct_table(
-            list(self._direct_entries.items()), self.direct_keys.shape[0]
-        )
-        self.direct_keys.copy_(keys.to(self.device))
-        self.direct_vals.copy_(vals.to(self.device))
-        self._direct_tombstones.clear()
-
     def direct_keys_owned_by(self, owner: int) -> List[bytes]:
         """Pubkeys whose DirectMap entry currently holds `owner`."""
-        return [self._direct_pubkeys[h] for h, o in self._direct_entries.items()
-                if o == owner]
+        return self.directs.keys_owned_by(owner)
 
     def apply_direct_updates(self, upserts, deletes) -> None:
         """Batched incremental DirectMap update: `upserts` is a list of
@@ -383,97 +367,16 @@ class GpuBrokerEngine:
 
         The host dicts stay the source of truth.  Within one call the last
         upsert of a key wins, and an upsert wins over a delete of the same
-        key.  An entry whose hash collides with a DIFFERENT registered key
-        is skipped and logged (remote entries must not raise).  Deletes
-        tombstone the value and leave the key in its slot; when live +
-        tombstoned slots would pass half the table and there is a tombstone
+        key.  An entry whose hash collides with a DIFFERENT registered key,
+        or is 0, is skipped and logged (remote entries must not raise).
+        Deletes tombstone the value and leave the key in its slot; when live
+        + tombstoned slots would pass half the table and there is a tombstone
         to reclaim, or the kernel reports an update that found no slot, the
         table is compacted by a rebuild.
         Raises RuntimeError("direct table full") if the live entries alone
         do not fit."""
         self.flush_membership()
-        ups: Dict[int, Tuple[bytes, int]] = {}
-        for pubkey, owner in upserts:
-            h = fnv1a64(pubkey, self.hash_seed)
-            prev = self._direct_pubkeys.get(h)
-            if prev is None and h in ups:
-                prev = ups[h][0]
-            if (prev is not None and prev != pubkey) or h == 0:
-                log.warning("direct routing-hash collision; skipping remote entry")
-                continue
-            ups[h] = (pubkey, int(owner))
-        dels: Dict[int, None] = {}   # insertion-ordered set
-        for pubkey in deletes:
-            h = fnv1a64(pubkey, self.hash_seed)
-            if h in ups or h in dels:
-                continue
-            if h in self._direct_entries and self._direct_pubkeys.get(h) == pubkey:
-                dels[h] = None
-        dels = list(dels)
-        S = self.direct_keys.shape[0]
-        live = len(self._direct_entries) - len(dels) + sum(
-            1 for h in ups if h not in self._direct_entries)
-        if live > S:
-            raise RuntimeError("direct table full")
-        for h in dels:
-            del self._direct_entries[h]
-            del self._direct_pubkeys[h]
-        for h, (pubkey, owner) in ups.items():
-            self._direct_entries[h] = owner
-            self._direct_pubkeys[h] = pubkey
-        self._push_direct([(h, o) for h, (_k, o) in ups.items()], dels)
-
-    def _push_direct(self, up_list: List[Tuple[int, int]], dels: List[int]) -> None:
-        """Bring the device table in line with the host dicts, which already
-        hold the change: `up_list` is (hash, owner) upserts, `dels` hashes to
-        tombstone, all distinct.  One K6 launch (or the CPU mirror), or a
-        rebuild where the tombstone rule or a failed insert asks for one."""
-        if not up_list and not dels:
-            return
-        S = self.direct_keys.shape[0]
-        tombstones = (self._direct_tombstones | set(dels)) - {h for h, _ in up_list}
-        # slots in use once this batch is in: live entries + tombstones
-        used = len(self._direct_entries) + len(tombstones)
-        # compaction reclaims tombstoned slots only: with none, a table past
-        # half full keeps taking incremental inserts (probe chains grow, as
-        # in any open-addressing table; size gpu_direct_table_size at twice
-        # the cluster's users to stay below it) and falls back to the
-        # rebuild through n_failed
-        if used > S // 2 and tombstones:
-            self._rebuild_direct_table()
-            return
-        self._direct_tombstones = tombstones
-        try:
-            if not self.use_gpu_ops:
-                from ..ops.reference import direct_apply
-
-                failed = direct_apply(self.direct_keys, self.direct_vals, up_list, dels)
-            else:
-                def i64(x: int) -> int:
-                    return x - (1 << 64) if x >= (1 << 63) else x
-
-                dev = self.device
-                up_keys = torch.tensor([i64(h) for h, _ in up_list],
-                                       dtype=torch.int64).to(dev)
-                up_owners = torch.tensor([o for _, o in up_list],
-                                         dtype=torch.int32).to(dev)
-                del_keys = torch.tensor([i64(h) for h in dels], dtype=torch.int64).to(dev)
-                self._ops.direct_apply(self.direct_keys, self.direct_vals, up_keys,
-                                       up_owners, del_keys, self._direct_failed)
-                # A 4-byte readback, also on a tick whose membership flush
-                # carries DirectMap changes: an insert that found no slot has
-                # to be repaired by the rebuild below BEFORE that tick's K5
-                # looks the key up.
-                failed = int(self._direct_failed.cpu()[0])
-                if failed:
-                    self._direct_failed.zero_()
-        except Exception:
-            # the host dicts already hold the update: bring the device table
-            # back in line with them before the error travels on
-            self._rebuild_direct_table()
-            raise
-        if failed:
-            self._rebuild_direct_table()
+        self.directs.update(upserts, deletes)
 
     # ---------------------------- membership log ----------------------------
     #
@@ -515,14 +418,6 @@ class GpuBrokerEngine:
             row[0] = (row[0] | clear) & ~set_
             row[1] = (row[1] | set_) & ~clear
 
-    def _queue_direct(self, h: int, owner: Optional[int]) -> None:
-        """owner None = delete.  Remembers whether the device table held the
-        hash before the first pending change, so a delete of an entry that
-        never reached the device is dropped at flush."""
-        prev = self._mship_direct.get(h)
-        on_device = prev[1] if prev is not None else h in self._direct_entries
-        self._mship_direct[h] = (owner, on_device)
-
     def queue_subscribe(self, recipient: int, topics: List[int]) -> None:
         self._check_recipient(recipient, self.n_recipients)
         self._queue_row(recipient, 0, self._topic_bits(topics), False)
@@ -535,18 +430,10 @@ class GpuBrokerEngine:
         """A user takes `slot`: its interest becomes exactly `topics`, its
         ring cursor is reset, hash(pubkey) -> slot is upserted.  Raises
         ValueError on a routing-hash collision with a different registered
-        key and RuntimeError when the DirectMap is full; a refusal leaves
-        the log and the host dicts untouched."""
+        key (or routing hash 0) and RuntimeError when the DirectMap is full;
+        a refusal leaves the log and the host dicts untouched."""
         self._check_recipient(slot, self.n_users)
-        h = self._direct_hash(pubkey)
-        if h == 0:
-            raise ValueError("routing hash 0 is the empty marker; refusing registration")
-        if h not in self._direct_entries \
-                and len(self._direct_entries) >= self.direct_keys.shape[0]:
-            raise RuntimeError("direct table full")
-        self._queue_direct(h, slot)
-        self._direct_pubkeys[h] = pubkey
-        self._direct_entries[h] = slot
+        self.directs.queue_upsert(pubkey, slot)
         self._queue_row(slot, 0, self._topic_bits(topics), True)
 
     def queue_leave(self, slot: int, pubkey: Optional[bytes]) -> None:
@@ -555,11 +442,7 @@ class GpuBrokerEngine:
         `pubkey` (None: no entry to delete)."""
         self._check_recipient(slot, self.n_users)
         if pubkey is not None:
-            h = fnv1a64(pubkey, self.hash_seed)
-            if h in self._direct_entries and self._direct_pubkeys.get(h) == pubkey:
-                self._queue_direct(h, None)
-                del self._direct_entries[h]
-                del self._direct_pubkeys[h]
+            self.directs.queue_delete(pubkey)
         self._queue_row(slot, 0, 0, True)
 
     def flush_membership(self) -> None:
@@ -567,8 +450,6 @@ class GpuBrokerEngine:
         (the model on the CPU engine), then the DirectMap changes through
         the incremental K6 path.  An empty log costs nothing."""
         if self._mship_rows:
-            import numpy as np
-
             rows, self._mship_rows = self._mship_rows, {}
             m64 = (1 << 64) - 1
             flat = []
@@ -587,9 +468,7 @@ class GpuBrokerEngine:
                     self._ctl_ops.membership_apply(self.sub_bitmap, self.ring_wpos,
                                                    recs.to(self.device))
                 else:
-                    from ..ops.reference import membership_apply
-
-                    membership_apply(self.sub_bitmap, self.ring_wpos, recs)
+                    ref.membership_apply(self.sub_bitmap, self.ring_wpos, recs)
             except Exception:
                 self._mship_rows = rows   # nothing applied: the rows stay pending
                 raise
@@ -599,11 +478,7 @@ class GpuBrokerEngine:
                          if row[2] and 0 <= r < self.n_recipients]
                 if reset:
                     self.demand[torch.tensor(reset, dtype=torch.int64).to(self.device)] = 0
-        if self._mship_direct:
-            pending, self._mship_direct = self._mship_direct, {}
-            up_list = [(h, o) for h, (o, _dev) in pending.items() if o is not None]
-            dels = [h for h, (o, on_device) in pending.items() if o is None and on_device]
-            self._push_direct(up_list, dels)
+        self.directs.flush()
 
     # ---------------------------- the hot tick ----------------------------
 
@@ -696,7 +571,7 @@ class GpuBrokerEngine:
         messages: [NB][W*64] counts + prefixes, per-user base/fit/dst."""
         NB = (M + 31) // 32
         W64 = self.W * 64
-        cur = getattr(self, "_k2b_scratch", None)
+        cur = self._k2b_scratch
         if cur is not None and cur[0] >= NB:
             return cur[1]
         o32 = dict(dtype=torch.int32, device=self.device)
@@ -911,8 +786,6 @@ class GpuBrokerEngine:
 
     def _tick_cpu(self, batch: bytes, offsets: List[int], origin=None,
                   ref_base: int = 0) -> TickStats:
-        from ..ops import reference as ref
-
         pr = ref.parse_batch(batch, offsets, self.hash_seed)
         M = len(offsets) - 1
         origin = self._origin_tensor(origin, M)
@@ -1069,9 +942,7 @@ class GpuBrokerEngine:
         if not self.loss_accounting:
             return
         if self._acct_ops is None:
-            from ..ops.reference import loss_scan
-
-            self._merge_losses(loss_scan(self.demand, self.ring_wpos))
+            self._merge_losses(ref.loss_scan(self.demand, self.ring_wpos))
             return
         self._acct_ops.loss_scan(self.demand, self.ring_wpos, self._lossy, self._n_lossy,
                                  self._n_lossy_host)
@@ -1098,53 +969,10 @@ class GpuBrokerEngine:
 
     def next_staging_index(self) -> int:
         """Which host staging buffer the NEXT drain_compact will fill."""
-        return getattr(self, "_staging_flip", 0)
+        return self._staging_flip
 
     def read_ring(self, user_idx: int, nbytes: Optional[int] = None) -> bytes:
         n = self.ring_bytes if nbytes is None else nbytes
         start = user_idx * self.ring_bytes
         return bytes(self.egress[start : start + n].to("cpu").numpy().tobytes())
 
-
-def parse_ring_records(ring: bytes, wpos: int, refbuf=None) -> List[Tuple[int, bytes]]:
-    """Parse delivery records out of a drained ring, ordered by sequence
-    number: [(seq, payload), ...].
-
-    A by-reference record (REF_FLAG set in its len word, no payload in the
-    ring) resolves to refbuf[ref_off : ref_off + len]; without a refbuf, or
-    with a range outside it, it raises ValueError.
-
-    Ring WRITE order is claim order: broadcasts are per-user ordered by
-    K2b, but K5b's direct-delivery claims are atomic and may interleave
-    out of order within a tick — the seq header restores the global
-    per-tick arrival order (stronger than the reference's per-connection
-    FIFO, sender.rs).  The sort is wrap-aware relative to the batch's
-    lowest seq."""
-    out = []
-    pos = 0
-    while pos + 16 <= wpos:
-        length = int.from_bytes(ring[pos : pos + 4], "little")
-        seq = int.from_bytes(ring[pos + 4 : pos + 8], "little")
-        if length & REF_FLAG:
-            length &= REF_FLAG - 1
-            ref_off = int.from_bytes(ring[pos + 8 : pos + 16], "little")
-            if refbuf is None:
-                raise ValueError("by-reference record without a reference buffer")
-            if ref_off + length > len(refbuf):
-                raise ValueError(
-                    f"by-reference record [{ref_off}, {ref_off + length}) outside "
-                    f"the {len(refbuf)}-byte reference buffer")
-            out.append((seq, bytes(refbuf[ref_off : ref_off + length])))
-            pos += RING_ALIGN
-            continue
-        payload = ring[pos + 16 : pos + 16 + length]
-        out.append((seq, payload))
-        pos += ring_rec(length)
-    if len(out) > 1:
-        # circular minimum (handles u32 seq wrap mid-batch)
-        base = out[0][0]
-        for s_, _ in out:
-            if (s_ - base) & 0xFFFFFFFF > 0x80000000:
-                base = s_
-        out.sort(key=lambda r: (r[0] - base) & 0xFFFFFFFF)
-    return out

@@ -16,8 +16,8 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from ..utils.keyhash import fnv1a64
-from ..broker.gpu_engine import REF_FLAG, ring_rec
+from ..utils.keyhash import as_i64 as _i64, fnv1a64
+from .ring_format import REF_FLAG, ring_rec
 
 
 @dataclass
@@ -29,11 +29,6 @@ class ParseResult:
     topics_cnt: torch.Tensor   # int32 [M]
     recip_hash: torch.Tensor   # int64 [M] (bit-cast u64)
     timestamp: torch.Tensor    # int64 [M]
-
-
-def _i64(x: int) -> int:
-    """Bit-cast u64 -> i64 for storage in torch int64 tensors."""
-    return x - (1 << 64) if x >= (1 << 63) else x
 
 
 def parse_batch(buf: bytes, offsets: List[int], hash_seed: int = 0) -> ParseResult:
@@ -504,5 +499,6 @@ def build_direct_table(entries: List[Tuple[int, int]], size: int) -> Tuple[torch
                 vals[slot] = owner
                 break
         else:
-            raise RuntimeError("direct table full")
+            # DirectMap admits no more entries than slots: not reached from it
+            raise RuntimeError(f"no free slot in a table of {size}")
     return keys, vals

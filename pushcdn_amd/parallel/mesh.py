@@ -24,6 +24,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from ..utils.keyhash import as_i64
 
 class RcclMesh:
     def __init__(self, device: torch.device, batch_capacity: int,
@@ -170,9 +171,8 @@ class RcclMesh:
             return [(0, batch, n_messages, batch_bytes)]
         assert batch.numel() == self.capacity
 
-        def _i64(w: int) -> int:
-            w &= (1 << 64) - 1
-            return w - (1 << 64) if w >= (1 << 63) else w
+        def _i64(w: int) -> int:   # the low 64 bits of w
+            return as_i64(w & ((1 << 64) - 1))
 
         def pack_bits(v: int) -> list:
             return [_i64(v >> (64 * i)) for i in range(4)]

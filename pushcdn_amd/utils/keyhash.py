@@ -20,6 +20,12 @@ _FNV_PRIME = 0x100000001B3
 _MASK = (1 << 64) - 1
 
 
+def as_i64(x: int) -> int:
+    """Bit-cast u64 -> i64: how a 64-bit hash or bitmap word is stored in a
+    torch int64 tensor."""
+    return x - (1 << 64) if x >= (1 << 63) else x
+
+
 def fnv1a64(data: bytes, seed: int = 0) -> int:
     h = _FNV_OFFSET ^ (seed & _MASK)
     for b in data:

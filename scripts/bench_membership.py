@@ -74,12 +74,12 @@ class Bench:
         self.sync()
         # DirectMap rebuilds (O(P) host work), counted per storm
         self.rebuilds = 0
-        real = self.eng._rebuild_direct_table
+        real = self.eng.directs.rebuild
 
         def counted():
             self.rebuilds += 1
             real()
-        self.eng._rebuild_direct_table = counted
+        self.eng.directs.rebuild = counted
 
     def sync(self):
         if self.cuda:
@@ -132,7 +132,7 @@ class Bench:
 
     def check(self, n_live: int) -> None:
         """The state both variants must leave: n_live registered users."""
-        assert len(self.eng._direct_entries) == n_live, (len(self.eng._direct_entries), n_live)
+        assert len(self.eng.directs.entries) == n_live, (len(self.eng.directs.entries), n_live)
         assert self.eng.pending_membership == 0
 
 

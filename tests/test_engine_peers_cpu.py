@@ -297,15 +297,15 @@ def test_apply_direct_updates_compacts_past_half_the_table():
     assert _engine_lookup(eng, first) == [-2] * 6
     eng.apply_direct_updates([(first[0], -3)], first[2:])         # 4 tombstones
     assert int((eng.direct_keys != 0).sum()) == 6                  # keys stay
-    assert len(eng._direct_tombstones) == 4
+    assert len(eng.directs.tombstones) == 4
     assert _engine_lookup(eng, first) == [-3, -2] + [INT32_MIN] * 4
     # 2 live + 4 tombstoned + 3 new = 9 > 16 / 2: compaction by rebuild
     more = [b"more-%d" % i for i in range(3)]
     eng.apply_direct_updates([(k, 7) for k in more], [])
-    assert not eng._direct_tombstones
+    assert not eng.directs.tombstones
     assert int((eng.direct_keys != 0).sum()) == 5                  # live entries only
     assert _engine_lookup(eng, first + more) == [-3, -2] + [INT32_MIN] * 4 + [7] * 3
-    assert sorted(eng._direct_entries.values()) == [-3, -2, 7, 7, 7]
+    assert sorted(eng.directs.entries.values()) == [-3, -2, 7, 7, 7]
     # a re-upsert of a deleted key after compaction is an ordinary insert
     eng.apply_direct_updates([(first[5], -4)], [])
     assert _engine_lookup(eng, [first[5]]) == [-4]
@@ -319,10 +319,10 @@ def test_apply_direct_updates_dedup_collision_and_full():
     assert eng.direct_keys_owned_by(-3) == [b"a"]
     # a hash that belongs to a different registered key: skipped, not raised
     h = fnv1a64(b"b", 0)
-    eng._direct_pubkeys[h] = b"someone-else"
+    eng.directs.pubkeys[h] = b"someone-else"
     eng.apply_direct_updates([(b"b", -4), (b"c", -4)], [b"b"])
     assert _engine_lookup(eng, [b"b", b"c"]) == [-2, -4]
-    eng._direct_pubkeys[h] = b"b"
+    eng.directs.pubkeys[h] = b"b"
     # the old API still rebuilds and keeps working next to the new one
     eng.register_direct(b"local", 3)
     eng.unregister_direct(b"a")
@@ -337,8 +337,8 @@ def test_apply_direct_updates_without_tombstones_stays_incremental(monkeypatch):
     incremental apply, no rebuild.  The first delete after that compacts."""
     eng = make_engine(direct_table_size=16)
     rebuilds = []
-    real = eng._rebuild_direct_table
-    monkeypatch.setattr(eng, "_rebuild_direct_table",
+    real = eng.directs.rebuild
+    monkeypatch.setattr(eng.directs, "rebuild",
                         lambda: (rebuilds.append(1), real())[1])
     keys = [b"k-%d" % i for i in range(10)]
     eng.apply_direct_updates([(k, -2) for k in keys[:6]], [])
@@ -346,7 +346,7 @@ def test_apply_direct_updates_without_tombstones_stays_incremental(monkeypatch):
     assert rebuilds == []
     assert _engine_lookup(eng, keys) == [-2] * 6 + [-3] * 4
     eng.apply_direct_updates([], [keys[0]])
-    assert rebuilds == [1] and not eng._direct_tombstones
+    assert rebuilds == [1] and not eng.directs.tombstones
     assert _engine_lookup(eng, keys) == [INT32_MIN] + [-2] * 5 + [-3] * 4
     assert int((eng.direct_keys != 0).sum()) == 9
 
@@ -363,4 +363,4 @@ def test_apply_direct_updates_failed_apply_resyncs_device_table(monkeypatch):
         eng.apply_direct_updates([(b"b", -3)], [b"a"])
     # host dicts and device table agree again
     assert _engine_lookup(eng, [b"a", b"b"]) == [INT32_MIN, -3]
-    assert eng.direct_keys_owned_by(-3) == [b"b"] and not eng._direct_tombstones
+    assert eng.direct_keys_owned_by(-3) == [b"b"] and not eng.directs.tombstones

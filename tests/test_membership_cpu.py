@@ -205,8 +205,8 @@ def test_join_and_leave_inside_one_flush_never_reach_the_table():
     eng.queue_leave(3, b"brief")
     eng.flush_membership()
     assert topics_of(eng, 3) == [] and lookup(eng, [b"brief"]) == [INT32_MIN]
-    assert int((eng.direct_keys != 0).sum()) == 0 and not eng._direct_tombstones
-    assert not eng._direct_entries and not eng._direct_pubkeys
+    assert int((eng.direct_keys != 0).sum()) == 0 and not eng.directs.tombstones
+    assert not eng.directs.entries and not eng.directs.pubkeys
 
 
 def test_leave_keeps_an_entry_that_moved_to_another_key_or_slot():
@@ -231,7 +231,7 @@ def test_log_is_bounded_by_recipients():
         eng.queue_leave(slot, b"u-%d" % slot)
         eng.queue_join(slot, b"v-%d" % slot, [slot + 1])
     assert eng.pending_membership == N_USERS
-    assert len(eng._mship_direct) <= 2 * N_USERS
+    assert len(eng.directs.pending) <= 2 * N_USERS
     with pytest.raises(IndexError):
         eng.queue_subscribe(N_USERS + P, [1])
     with pytest.raises(IndexError):
@@ -242,21 +242,45 @@ def test_log_is_bounded_by_recipients():
 # refusal, program order with the immediate API, the empty flush
 # ===========================================================================
 
+# every way to register `key` for user `slot`; the bulk call has an entry on
+# either side of it, which a refusal must leave out as well
+REGISTRATIONS = {
+    "queue_join": lambda eng, slot, key: eng.queue_join(slot, key, [5]),
+    "register_direct": lambda eng, slot, key: eng.register_direct(key, slot),
+    "register_direct_bulk": lambda eng, slot, key: eng.register_direct_bulk(
+        [(b"ahead", 3), (key, slot), (b"behind", 4)]),
+}
+
+
+def mirror_state(eng):
+    """Copies of the log, the DirectMap's host mirror and its device table."""
+    d = eng.directs
+    return dict(rows={r: list(v) for r, v in eng._mship_rows.items()},
+                pending=dict(d.pending), entries=dict(d.entries), pubkeys=dict(d.pubkeys),
+                tombstones=set(d.tombstones), direct_keys=eng.direct_keys.clone(),
+                direct_vals=eng.direct_vals.clone())
+
+
+def assert_mirror_unchanged(eng, before, what):
+    for name, now in mirror_state(eng).items():
+        same = torch.equal(now, before[name]) if torch.is_tensor(now) else now == before[name]
+        assert same, f"{what}: {name} changed"
+
+
 def test_collision_refusal_changes_nothing():
-    eng = make_engine()
-    eng.queue_join(1, b"first", [1])
-    h = fnv1a64(b"victim", SEED)
-    eng._direct_pubkeys[h] = b"someone-else"     # forge the collision
-    eng._direct_entries[h] = 9
-    rows = {r: list(v) for r, v in eng._mship_rows.items()}
-    direct = dict(eng._mship_direct)
-    entries, pubkeys = dict(eng._direct_entries), dict(eng._direct_pubkeys)
-    with pytest.raises(ValueError, match="collision"):
-        eng.queue_join(2, b"victim", [5])
-    assert {r: list(v) for r, v in eng._mship_rows.items()} == rows
-    assert eng._mship_direct == direct
-    assert eng._direct_entries == entries and eng._direct_pubkeys == pubkeys
-    assert eng.pending_membership == 1
+    for name, register in REGISTRATIONS.items():
+        eng = make_engine()
+        eng.queue_join(1, b"first", [1])
+        if name != "queue_join":
+            eng.flush_membership()   # the immediate methods flush first, refused or not
+        h = fnv1a64(b"victim", SEED)
+        eng.directs.pubkeys[h] = b"someone-else"     # forge the collision
+        eng.directs.entries[h] = 9
+        before = mirror_state(eng)
+        with pytest.raises(ValueError, match="collision"):
+            register(eng, 2, b"victim")
+        assert_mirror_unchanged(eng, before, name)
+        assert eng.pending_membership == (1 if name == "queue_join" else 0)
 
 
 def test_full_table_refusal_changes_nothing():
@@ -265,10 +289,48 @@ def test_full_table_refusal_changes_nothing():
     eng.queue_join(1, b"b", [1])
     with pytest.raises(RuntimeError, match="direct table full"):
         eng.queue_join(2, b"c", [1])
-    assert eng.pending_membership == 2 and len(eng._direct_entries) == 2
+    assert eng.pending_membership == 2 and len(eng.directs.entries) == 2
     eng.queue_join(1, b"b", [2])                 # a key that is in: no refusal
     eng.flush_membership()
     assert lookup(eng, [b"a", b"b", b"c"]) == [0, 1, INT32_MIN]
+    # the immediate methods: the same refusal, and the table still rebuilds after it
+    for name in ("register_direct", "register_direct_bulk"):
+        eng = make_engine(direct_table_size=2)
+        eng.register_direct(b"a", 0)
+        eng.register_direct(b"b", 1)
+        before = mirror_state(eng)
+        with pytest.raises(RuntimeError, match="direct table full"):
+            if name == "register_direct":
+                eng.register_direct(b"c", 2)
+            else:
+                eng.register_direct_bulk([(b"b", 5), (b"c", 2)])
+        assert_mirror_unchanged(eng, before, name)
+        eng.register_direct(b"b", 6)             # a key that is in: no refusal
+        assert lookup(eng, [b"a", b"b", b"c"]) == [0, 6, INT32_MIN]
+
+
+def test_hash_zero_refusal_changes_nothing(monkeypatch):
+    """Routing hash 0 is the table's empty marker: a key that hashes to it is
+    refused like a collision, before anything changes; a remote entry with
+    it is skipped."""
+    from pushcdn_amd.broker import direct_map
+
+    monkeypatch.setattr(direct_map, "fnv1a64",
+                        lambda key, seed=0: 0 if key == b"zero" else fnv1a64(key, seed))
+    for name, register in REGISTRATIONS.items():
+        eng = make_engine()
+        eng.queue_join(1, b"first", [1])
+        if name != "queue_join":
+            eng.flush_membership()
+        before = mirror_state(eng)
+        with pytest.raises(ValueError, match="hash 0"):
+            register(eng, 2, b"zero")
+        assert_mirror_unchanged(eng, before, name)
+    eng = make_engine()
+    eng.apply_direct_updates([(b"remote", -2), (b"zero", -3)], [b"zero"])
+    assert list(eng.directs.pubkeys.values()) == [b"remote"]
+    assert lookup(eng, [b"remote"]) == [-2]
+    assert int((eng.direct_keys != 0).sum()) == 1
 
 
 def test_immediate_call_flushes_the_pending_log_first():
@@ -309,7 +371,7 @@ def test_empty_flush_performs_no_op_call(monkeypatch):
     calls = []
     monkeypatch.setattr(ref, "membership_apply", lambda *a: calls.append("membership_apply"))
     monkeypatch.setattr(ref, "direct_apply", lambda *a: calls.append("direct_apply"))
-    monkeypatch.setattr(eng, "_rebuild_direct_table", lambda: calls.append("rebuild"))
+    monkeypatch.setattr(eng.directs, "rebuild", lambda: calls.append("rebuild"))
     eng.flush_membership()
     eng.drain_cursors()
     eng.drain_compact()
@@ -476,8 +538,8 @@ def test_sequence_is_a_real_workload():
 def test_batched_sequence_equals_immediate_api(monkeypatch):
     eng = make_engine()
     rebuilds = []
-    real = eng._rebuild_direct_table
-    monkeypatch.setattr(eng, "_rebuild_direct_table",
+    real = eng.directs.rebuild
+    monkeypatch.setattr(eng.directs, "rebuild",
                         lambda: (rebuilds.append(1), real())[1])
     assert_same_as_immediate(eng)
     # the point of the log: not one rebuild per connect and disconnect

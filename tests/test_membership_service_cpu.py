@@ -6,8 +6,8 @@ through the per-topic immediate methods or a DirectMap rebuild."""
 import asyncio
 
 T1, T2 = 5, 200
-IMMEDIATE = ("subscribe", "unsubscribe", "register_direct", "unregister_direct",
-             "_rebuild_direct_table")
+IMMEDIATE = ("subscribe", "unsubscribe", "register_direct", "unregister_direct")
+REBUILD = ("rebuild",)       # of the engine's DirectMap, eng.directs
 QUEUED = ("queue_join", "queue_leave", "queue_subscribe", "queue_unsubscribe")
 
 
@@ -68,6 +68,7 @@ def test_batched_membership_over_tcp(tmp_path):
                                 gpu_batched_membership=True))
         eng = broker._engine
         immediate = spy_on(eng, IMMEDIATE)
+        rebuilds = spy_on(eng.directs, REBUILD)
         queued = spy_on(eng, QUEUED)
         await broker.start()
         await broker.discovery.perform_heartbeat(0, 60)
@@ -127,7 +128,7 @@ def test_batched_membership_over_tcp(tmp_path):
         await sender.send_broadcast_message([T1], b"fresh")
         assert await recv(d) == b"fresh"
 
-        assert immediate == {n: 0 for n in IMMEDIATE}
+        assert immediate == {n: 0 for n in IMMEDIATE} and rebuilds == {"rebuild": 0}
         assert queued == {"queue_join": 3, "queue_leave": 1, "queue_subscribe": 1,
                           "queue_unsubscribe": 1}
         ticks = [t for t in broker._tasks if t.get_name() == "gpu-tick"]

@@ -291,7 +291,7 @@ def test_direct_hash_collision_refused():
     eng.register_direct(b"alice-key", 1)
     # a DIFFERENT key landing on the same 64-bit hash is refused
     h = fnv1a64(b"bob-key", 99)
-    eng._direct_pubkeys[h] = b"someone-else"
+    eng.directs.pubkeys[h] = b"someone-else"
     with pytest.raises(ValueError):
         eng.register_direct(b"bob-key", 2)
 
