@@ -432,6 +432,36 @@ PYBIND11_MODULE(pushcdn_core, m) {
                  return p.send_rings_batch((const uint8_t*)info.ptr, ids, starts, ends);
              },
              "batched tick drain: one call for all users' compacted rings")
+        .def("send_framed_batch",
+             [](net::Pump& p, py::buffer base, const std::vector<int64_t>& ids,
+                const std::vector<int64_t>& starts, const std::vector<int64_t>& lens,
+                const std::vector<int64_t>& cnts) {
+                 py::buffer_info info = base.request();
+                 if (info.itemsize != 1)
+                     throw std::runtime_error("send_framed_batch: buffer must be bytes");
+                 if (ids.size() != starts.size() || ids.size() != lens.size()
+                     || ids.size() != cnts.size())
+                     throw std::runtime_error("send_framed_batch: length mismatch");
+                 for (size_t j = 0; j < ids.size(); ++j) {
+                     if (starts[j] < 0 || lens[j] < 0 || starts[j] > info.size
+                         || lens[j] > info.size - starts[j])
+                         throw std::runtime_error("send_framed_batch: range beyond buffer");
+                     if (cnts[j] < -1)
+                         throw std::runtime_error("send_framed_batch: frame count below -1");
+                 }
+                 // one copy of every recipient's bytes: never under the GIL
+                 py::gil_scoped_release nogil;
+                 return p.send_framed_batch((const uint8_t*)info.ptr, ids, starts, lens, cnts);
+             },
+             "batched tick drain of socket-ready frames (the framed drain)")
+        .def_static("check_frames",
+             [](py::buffer data, int64_t cnt) {
+                 py::buffer_info info = data.request();
+                 if (info.itemsize != 1)
+                     throw std::runtime_error("check_frames: buffer must be bytes");
+                 return net::Pump::check_frames((const uint8_t*)info.ptr, (size_t)info.size, cnt);
+             },
+             "true iff the buffer is exactly cnt length-prefixed frames")
         .def("send_ring_ref", [](net::Pump& p, int64_t id, py::buffer ring, size_t wpos,
                                  py::buffer ref) {
             py::buffer_info info = ring.request();

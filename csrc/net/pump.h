@@ -295,6 +295,87 @@ public:
         return out;
     }
 
+    // One bounds-checked walk over the length prefixes of `len` bytes that
+    // claim to be `cnt` frames [u32 BE length][body] back to back (the framed
+    // drain's output, gpu_engine.drain_framed): true iff there are exactly
+    // cnt frames, each at most kMaxMessageSize, tiling [0, len) exactly.
+    // Reads 4 bytes per frame and no body.
+    static bool check_frames(const uint8_t* p, size_t len, int64_t cnt) {
+        if (cnt < 0) return false;
+        size_t pos = 0;
+        int64_t n = 0;
+        while (pos < len) {
+            if (len - pos < 4 || n == cnt) return false;
+            uint32_t be;
+            memcpy(&be, p + pos, 4);
+            const uint64_t body = ntohl(be);
+            if (body > kMaxMessageSize || body > len - pos - 4) return false;
+            pos += 4 + (size_t)body;
+            ++n;
+        }
+        return n == cnt;
+    }
+
+    // send_rings_batch for a framed drain: entry j is lens[j] bytes at
+    // base + starts[j] that already ARE cnts[j] socket-ready frames in
+    // arrival order, so they are checked (check_frames) and queued verbatim
+    // with one copy: no record parse, no sort, no second body copy.  An entry
+    // that fails the check queues nothing and reports count -2: a bad prefix
+    // must never reach a client, it would desynchronise the stream for good.
+    // cnts[j] == -1: the entry is a raw ring prefix (the drain's ring mode)
+    // and goes through build_ring_frames as in send_rings_batch.
+    // Returns per-entry [count, payload_bytes] interleaved; count -1 = the
+    // connection is gone.  Everything but the outbox push happens outside
+    // the mutex.
+    std::vector<int64_t> send_framed_batch(const uint8_t* base,
+                                           const std::vector<int64_t>& ids,
+                                           const std::vector<int64_t>& starts,
+                                           const std::vector<int64_t>& lens,
+                                           const std::vector<int64_t>& cnts) {
+        size_t n_users = ids.size();
+        std::vector<int64_t> counts(n_users, 0);
+        std::vector<std::string> bufs(n_users);
+        std::vector<int64_t> payload(n_users, 0);
+        for (size_t j = 0; j < n_users; ++j) {
+            const uint8_t* p = base + starts[j];
+            const size_t len = (size_t)lens[j];
+            if (cnts[j] == -1) {
+                auto r = build_ring_frames(p, len, &bufs[j]);
+                counts[j] = r.first;
+                payload[j] = r.second;
+            } else if (check_frames(p, len, cnts[j])) {
+                bufs[j].assign((const char*)p, len);
+                counts[j] = cnts[j];
+                payload[j] = (int64_t)len - 4 * cnts[j];
+            } else {
+                counts[j] = -2;
+            }
+        }
+        bool any = false;
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            for (size_t j = 0; j < n_users; ++j) {
+                auto it = conns_.find(ids[j]);
+                if (it == conns_.end() || it->second.closed || it->second.soft_closing) {
+                    counts[j] = -1;
+                    continue;
+                }
+                if (counts[j] > 0) {
+                    it->second.outbox.emplace_back(std::move(bufs[j]));
+                    it->second.want_write = true;
+                    any = true;
+                }
+            }
+        }
+        if (any) wake();
+        std::vector<int64_t> out(2 * n_users);
+        for (size_t j = 0; j < n_users; ++j) {
+            out[2 * j] = counts[j];
+            out[2 * j + 1] = counts[j] < 0 ? 0 : payload[j];
+        }
+        return out;
+    }
+
     // bytes queued but not yet written (backpressure signal for Python)
     int64_t send_backlog(int64_t id) {
         std::lock_guard<std::mutex> g(mu_);

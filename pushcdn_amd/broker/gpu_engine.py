@@ -35,6 +35,10 @@ per-recipient accumulator, demand (int64 [R]), takes the ring bytes every
 tick WANTED to deliver (K9); at a drain demand[r] - ring_wpos[r] is what
 recipient r lost (K10), reported by take_losses().
 
+Framed drain (drain_framed): K11 hands every recipient's records over as
+socket-ready [u32 big-endian len][message] frames in seq order instead of raw
+ring records, so the host neither parses nor sorts nor re-copies them.
+
 CPU mode (device="cpu") runs the pure-Python mirrors from ops.reference so
 the engine's semantics are testable without a GPU.
 """
@@ -51,7 +55,8 @@ import torch
 
 from ..ops import reference as ref
 # the ring record format is re-exported: callers import it from here
-from ..ops.ring_format import RING_ALIGN, REF_FLAG, parse_ring_records, ring_rec  # noqa: F401
+from ..ops.ring_format import (FRAME_SORT_MAX, RING_ALIGN, REF_FLAG,  # noqa: F401
+                               parse_frames, parse_ring_records, ring_rec)
 from ..utils.keyhash import as_i64
 from .direct_map import DirectMap
 
@@ -223,6 +228,12 @@ class GpuBrokerEngine:
         self._staging_dev: Optional[torch.Tensor] = None
         self._staging_host: Optional[List[torch.Tensor]] = None
         self._staging_flip = 0
+        # drain_framed's extras, made by its first call: the extension, K11's
+        # record index (as large as the device staging) and the per-recipient
+        # frame_len / frame_cnt on the device and in pinned host memory
+        self._drain_ops = None
+        self._frame_index: Optional[torch.Tensor] = None
+        self._frame_meta = None
         self._k2b_scratch = None  # (blocks it serves, block-K2b buffers)
         if self.use_gpu_ops:
             o32 = dict(dtype=torch.int32, device=dev)
@@ -882,30 +893,61 @@ class GpuBrokerEngine:
             refbuf = b"".join(bytes(b) for b in batches)
         return (*self._drain_compact(), refbuf)
 
-    def _drain_compact(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def drain_framed(self):
+        """drain_compact with the per-record work done on the device: returns
+        (wpos, offsets, frame_len, frame_cnt, staging), all on the host.
+        Recipient r's bytes are staging[offsets[r] : offsets[r] + frame_len[r]]:
+        frame_cnt[r] frames [u32 big-endian len][message] back to back, in
+        the order parse_ring_records gives, ready for the socket.
+        frame_cnt[r] == -1 (only for an out-of-order ring of more than
+        FRAME_SORT_MAX records, which a drain per tick never produces): the
+        bytes are the raw ring prefix, frame_len[r] == wpos[r].  Not with
+        ref_threshold: a by-reference record's body is in host memory."""
+        if self.ref_threshold is not None:
+            raise ValueError("drain_framed cannot frame by-reference records: "
+                             "the engine was built with a ref_threshold")
+        self.flush_membership()
+        self._discard_ref_batches()
+        return self._drain_compact(framed=True)
+
+    def _drain_compact(self, framed: bool = False):
+        """drain_compact's body; framed: drain_framed's, which differs in the
+        kernel that fills the staging (K11 for K7) and in the two per-recipient
+        arrays that come back with it."""
+        R = self.n_recipients
         self._scan_losses()
         if not self.use_gpu_ops:
             wpos = self.ring_wpos.detach().clone()
             self.ring_wpos.zero_()
-            offsets = torch.zeros(self.n_recipients + 1, dtype=torch.int64)
+            offsets = torch.zeros(R + 1, dtype=torch.int64)
             torch.cumsum(wpos, 0, out=offsets[1:])
             total = int(offsets[-1])
             staging = torch.empty(total, dtype=torch.uint8)
-            for u in range(self.n_recipients):
+            if framed:
+                frame_len = torch.zeros(R, dtype=torch.int64)
+                frame_cnt = torch.zeros(R, dtype=torch.int32)
+                ref.frame_rings(self.egress, self.ring_bytes, wpos, offsets[:R], staging,
+                                frame_len, frame_cnt)
+                return wpos, offsets, frame_len, frame_cnt, staging
+            for u in range(R):
                 n = int(wpos[u])
                 if n:
                     s = u * self.ring_bytes
                     staging[int(offsets[u]):int(offsets[u + 1])] = self.egress[s:s + n]
             return wpos, offsets, staging
-        wpos_dev = self.ring_wpos  # read by K7 before the reset below
+        wpos_dev = self.ring_wpos  # read by K7 / K11 before the reset below
         wpos = wpos_dev.detach().to("cpu")  # sync: cursor readback
         self._collect_losses()
-        offsets = torch.zeros(self.n_recipients + 1, dtype=torch.int64)
+        offsets = torch.zeros(R + 1, dtype=torch.int64)
         torch.cumsum(wpos, 0, out=offsets[1:])
         total = int(offsets[-1])
         if total == 0:
             self.ring_wpos.zero_()
-            return wpos, offsets, torch.empty(0, dtype=torch.uint8)
+            empty = torch.empty(0, dtype=torch.uint8)
+            if framed:
+                return (wpos, offsets, torch.zeros(R, dtype=torch.int64),
+                        torch.zeros(R, dtype=torch.int32), empty)
+            return wpos, offsets, empty
         # DOUBLE-buffered host staging: the caller may still be writing the
         # previous drain's frames to sockets (pipelined drains) while this
         # tick compacts into the other buffer; callers must not reuse a
@@ -919,17 +961,53 @@ class GpuBrokerEngine:
                 torch.empty(cap, dtype=torch.uint8, pin_memory=self.is_cuda)
                 for _ in range(2)
             ]
-        dst_off = offsets[: self.n_recipients].to(self.device, non_blocking=True)
-        max_chunks = (int(wpos.max()) + (64 << 10) - 1) // (64 << 10)
-        self._ops.compact_rings(self.egress, self.ring_bytes, wpos_dev, dst_off,
-                                self._staging_dev, max_chunks)
-        self.ring_wpos.zero_()  # stream-ordered after K7's reads
+        dst_off = offsets[:R].to(self.device, non_blocking=True)
+        if framed:
+            meta = self._frame_rings(wpos_dev, dst_off, int(wpos.max()))
+        else:
+            max_chunks = (int(wpos.max()) + (64 << 10) - 1) // (64 << 10)
+            self._ops.compact_rings(self.egress, self.ring_bytes, wpos_dev, dst_off,
+                                    self._staging_dev, max_chunks)
+        self.ring_wpos.zero_()  # stream-ordered after K7's / K11's reads
         host = self._staging_host[idx]
         if host.numel() < total:  # staging grew since this buffer was made
             host = self._staging_host[idx] = torch.empty(
                 self._staging_dev.numel(), dtype=torch.uint8, pin_memory=self.is_cuda)
         host[:total].copy_(self._staging_dev[:total])  # sync D2H
+        if framed:
+            # the two small copies were queued ahead of the D2H above, whose
+            # synchronise made them readable
+            return wpos, offsets, meta[0].clone(), meta[1].clone(), host[:total]
         return wpos, offsets, host[:total]
+
+    def _frame_rings(self, wpos_dev, dst_off, max_wpos: int):
+        """K11 into the device staging, and frame_len / frame_cnt on their way
+        to pinned host memory (not waited for).  Returns the two host tensors."""
+        if self._drain_ops is None:
+            from ..ops import get_gpu_drain_ops
+
+            self._drain_ops = get_gpu_drain_ops()
+        R = self.n_recipients
+        if self._frame_meta is None:
+            self._frame_meta = (
+                torch.empty(R, dtype=torch.int64, device=self.device),
+                torch.empty(R, dtype=torch.int32, device=self.device),
+                torch.empty(R, dtype=torch.int64, pin_memory=self.is_cuda),
+                torch.empty(R, dtype=torch.int32, pin_memory=self.is_cuda),
+            )
+        n_index = self._staging_dev.numel() // 16
+        if self._frame_index is None or self._frame_index.shape[0] < n_index:
+            self._frame_index = torch.empty((n_index, 4), dtype=torch.int32,
+                                            device=self.device)
+        len_dev, cnt_dev, len_host, cnt_host = self._frame_meta
+        chunk = self._drain_ops.CHUNK_BYTES
+        max_chunks = (min(max_wpos, self.ring_bytes) + chunk - 1) // chunk
+        self._drain_ops.frame_rings(self.egress, self.ring_bytes, wpos_dev, dst_off,
+                                    self._staging_dev, len_dev, cnt_dev, self._frame_index,
+                                    max_chunks)
+        len_host.copy_(len_dev, non_blocking=True)
+        cnt_host.copy_(cnt_dev, non_blocking=True)
+        return len_host, cnt_host
 
     # --------------------------- loss accounting ---------------------------
 
@@ -968,7 +1046,8 @@ class GpuBrokerEngine:
         return losses
 
     def next_staging_index(self) -> int:
-        """Which host staging buffer the NEXT drain_compact will fill."""
+        """Which host staging buffer the NEXT drain_compact or drain_framed
+        will fill."""
         return self._staging_flip
 
     def read_ring(self, user_idx: int, nbytes: Optional[int] = None) -> bytes:

@@ -74,6 +74,9 @@ class MeshBroker(Broker):
     # the collective tick has its own drain: no loss accounting here, so
     # config.gpu_overflow_policy has no effect
     OVERFLOW_POLICY = False
+    # and it dispatches drain_compact's ring records itself, so
+    # config.gpu_framed_drain has no effect
+    FRAMED_DRAIN = False
 
     def __init__(self, config: BrokerConfig, batch_capacity: int = 1 << 22,
                  interest_routed: Optional[bool] = None) -> None:

@@ -125,6 +125,12 @@ class BrokerConfig:
     # "evict" also removes that user or broker once what did fit has been
     # sent, the reference's send-or-remove (user/sender.rs).
     gpu_overflow_policy: str = "ignore"
+    # framed drain on the GPU plane: the drain hands every recipient's
+    # deliveries over as socket-ready length-prefixed frames in arrival order
+    # (K11), and the native pump queues them with one check and one copy.
+    # Off: raw ring records, parsed, sorted and framed on the host, as before.
+    # Not together with gpu_ref_threshold.
+    gpu_framed_drain: bool = False
 
 
 @dataclass
@@ -151,6 +157,9 @@ class Broker:
     # MeshBroker overrides to False: its collective tick drains on its own,
     # so config.gpu_overflow_policy has no effect there
     OVERFLOW_POLICY = True
+    # MeshBroker overrides to False for the same reason, so
+    # config.gpu_framed_drain has no effect there
+    FRAMED_DRAIN = True
 
     def __init__(self, config: BrokerConfig) -> None:
         from ..proto.transports.tcp import Tcp
@@ -190,6 +199,11 @@ class Broker:
         self._overflow_policy = (config.gpu_overflow_policy
                                  if config.data_plane == "gpu" and type(self).OVERFLOW_POLICY
                                  else "ignore")
+        self._framed_drain = (config.data_plane == "gpu" and config.gpu_framed_drain
+                              and type(self).FRAMED_DRAIN)
+        if self._framed_drain and self._ref_threshold is not None:
+            raise ValueError("gpu_framed_drain cannot be combined with gpu_ref_threshold: "
+                             "a by-reference record's body is not on the device")
         if config.data_plane == "gpu":
             from .gpu_engine import GpuBrokerEngine
 
@@ -933,7 +947,12 @@ class Broker:
                 pass
         # refbuf: the host batch this tick's by-reference records point
         # into; the dispatch closure keeps it alive until its sends are queued
-        if self._ref_threshold is not None:
+        framed = None
+        if self._framed_drain:
+            # (frame_len, frame_cnt): staging holds socket-ready frames
+            wpos, offsets, *framed, staging = self._engine.drain_framed()
+            refbuf = None
+        elif self._ref_threshold is not None:
             wpos, offsets, staging, refbuf = self._engine.drain_compact_ref()
         else:
             wpos, offsets, staging = self._engine.drain_compact()
@@ -953,7 +972,7 @@ class Broker:
                     await asyncio.shield(prev)
                 except Exception:
                     pass
-            await self._dispatch_egress(wpos, offsets, staging, peers, refbuf)
+            await self._dispatch_egress(wpos, offsets, staging, peers, refbuf, framed)
             # after the delivered prefix went to the sockets: what fitted is
             # still sent, as the reference sends everything before a failed send
             if overflowed and self._overflow_policy == "evict":
@@ -1012,11 +1031,28 @@ class Broker:
             GPU_RING_EVICTIONS.inc()
 
     async def _dispatch_egress(self, wpos, offsets, staging, peers=(),
-                               refbuf=None) -> None:
+                               refbuf=None, framed=None) -> None:
         """`peers`: [(broker, peer slot, handle)] as of the drain that
         produced wpos/offsets/staging.  `refbuf`: that drain's reference
-        buffer (drain_compact_ref), None when by-reference delivery is off."""
-        from .gpu_engine import parse_ring_records
+        buffer (drain_compact_ref), None when by-reference delivery is off.
+        `framed`: drain_framed's (frame_len, frame_cnt) when staging holds
+        socket-ready frames, None when it holds ring records."""
+        from .gpu_engine import parse_frames, parse_ring_records
+
+        def extent(r):
+            """(start, end, frame count or None) of recipient r's bytes."""
+            start = int(offsets[r])
+            if framed is None:
+                return start, int(offsets[r + 1]), None
+            return start, start + int(framed[0][r]), int(framed[1][r])
+
+        def payloads(r, n):
+            """Recipient r's messages in send order, parsed in Python."""
+            start, end, cnt = extent(r)
+            data = bytes(staging[start:end].numpy().tobytes())
+            if cnt is not None and cnt >= 0:
+                return parse_frames(data)
+            return [p for _seq, p in parse_ring_records(data, n, refbuf)]
 
         by_pump = {}        # pump -> [(pubkey, cid, start, end)]
         fallback = []       # (slot, pubkey, nbytes)
@@ -1033,8 +1069,7 @@ class Broker:
                 except Exception:
                     await self.remove_user(pubkey)
                     continue
-                by_pump.setdefault(p, []).append(
-                    (pubkey, cid, int(offsets[slot]), int(offsets[slot + 1])))
+                by_pump.setdefault(p, []).append((pubkey, cid, *extent(slot)))
                 continue
             fallback.append((slot, pubkey, n))
         # peer rings drain like user rings (records are whole wire messages);
@@ -1056,8 +1091,7 @@ class Broker:
                 except Exception:
                     await self.remove_broker(broker)
                     continue
-                by_pump.setdefault(p, []).append(
-                    (broker, cid, int(offsets[ring_idx]), int(offsets[ring_idx + 1])))
+                by_pump.setdefault(p, []).append((broker, cid, *extent(ring_idx)))
                 continue
             peer_fallback.append((ring_idx, broker, n, handle))
         if by_pump:
@@ -1074,6 +1108,15 @@ class Broker:
                 per = (len(entries) + nshards - 1) // nshards
                 for i in range(0, len(entries), per):
                     chunk = entries[i:i + per]
+                    if framed is not None:
+                        jobs.append((chunk, loop.run_in_executor(
+                            None, pump.send_framed_batch, view,
+                            [e[1] for e in chunk],
+                            [e[2] for e in chunk],
+                            [e[3] - e[2] for e in chunk],
+                            [e[4] for e in chunk],
+                        )))
+                        continue
                     if refbuf is not None:
                         call = (pump.send_rings_batch_ref, view, refbuf)
                     else:
@@ -1089,10 +1132,16 @@ class Broker:
 
             total_payload = 0
             for (chunk, _f), flat in zip(jobs, results):
-                for i, (pubkey, _cid, _s, _e) in enumerate(chunk):
+                for i, (pubkey, _cid, _s, _e, _n) in enumerate(chunk):
                     cnt = flat[2 * i]
                     total_payload += flat[2 * i + 1]
-                    if cnt < 0:
+                    if cnt == -2:
+                        # the pump refused the range: nothing was queued, and
+                        # the recipient loses this tick, not its connection
+                        log.error("framed drain: malformed frames for %s; tick skipped",
+                                  pubkey if isinstance(pubkey, BrokerIdentifier)
+                                  else ident(pubkey))
+                    elif cnt < 0:
                         if isinstance(pubkey, BrokerIdentifier):
                             await self.remove_broker(pubkey)
                         else:
@@ -1104,28 +1153,29 @@ class Broker:
                          .tobytes())
             if self.connections.brokers.get(broker) is not handle:
                 continue
-            sink = self._ring_sink(handle.connection, refbuf)
+            sink = self._ring_sink(handle.connection, refbuf) \
+                if framed is None or framed[1][ring_idx] < 0 else None
             if sink is not None:
                 try:
                     sink(ring, n)
                 except Exception:
                     await self.remove_broker(broker)
             else:
-                for _seq, payload in parse_ring_records(ring, n, refbuf):
+                for payload in payloads(ring_idx, n):
                     await self.try_send_to_broker(broker, Bytes(payload))
         for slot, pubkey, n in fallback:
             ring = bytes(staging[int(offsets[slot]):int(offsets[slot + 1])].numpy()
                          .tobytes())
             handle = self.connections.users.get(pubkey)
             sink = self._ring_sink(handle.connection, refbuf) \
-                if handle is not None else None
+                if handle is not None and (framed is None or framed[1][slot] < 0) else None
             if sink is not None:
                 try:
                     sink(ring, n)
                 except Exception:
                     await self.remove_user(pubkey)
             else:
-                for _seq, payload in parse_ring_records(ring, n, refbuf):
+                for payload in payloads(slot, n):
                     await self.try_send_to_user(pubkey, Bytes(payload))
 
     @staticmethod

@@ -69,6 +69,10 @@ def _broker_args(p: argparse.ArgumentParser) -> None:
                    help="GPU data plane: what to do about a recipient whose egress ring "
                         "overflowed: nothing (deliveries are dropped silently), count "
                         "the lost bytes per recipient, or count and disconnect it")
+    p.add_argument("--gpu-framed-drain", action="store_true",
+                   help="GPU data plane: frame and order every delivery on the device, "
+                        "so the drain hands the sockets ready bytes (not with "
+                        "--gpu-ref-threshold)")
     p.add_argument("--user-transport", choices=["tcp", "tcp-tls", "tcp-native", "quic", "quic-native"],
                    default="tcp", help="user-plane transport (tcp-native = C++ epoll "
                                        "pump; quic[-native] = QUIC-profile over UDP)")
@@ -95,6 +99,7 @@ def cmd_broker(args) -> None:
         gpu_ref_threshold=args.gpu_ref_threshold,
         gpu_batched_membership=args.gpu_batched_membership,
         gpu_overflow_policy=args.gpu_overflow_policy,
+        gpu_framed_drain=args.gpu_framed_drain,
         user_protocol=_transport(args.user_transport),
         broker_protocol=_transport(args.broker_transport),
     )

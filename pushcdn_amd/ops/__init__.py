@@ -77,3 +77,24 @@ def get_gpu_acct_ops():
             pass
     _gpu_acct_mod = build_gpu_acct()
     return _gpu_acct_mod
+
+
+_gpu_drain_mod = None
+
+
+def get_gpu_drain_ops():
+    """The framed-drain extension (``pushcdn_gpu_drain``: K11 frame_rings),
+    under the same rule as ``get_gpu_ops()``."""
+    global _gpu_drain_mod
+    if _gpu_drain_mod is not None:
+        return _gpu_drain_mod
+    from .build import GPU_DRAIN_BUILD_DIR, build_gpu_drain, load_gpu_drain_prebuilt
+
+    if (GPU_DRAIN_BUILD_DIR / "pushcdn_gpu_drain.so").exists():
+        try:
+            _gpu_drain_mod = load_gpu_drain_prebuilt()
+            return _gpu_drain_mod
+        except ImportError:
+            pass
+    _gpu_drain_mod = build_gpu_drain()
+    return _gpu_drain_mod

@@ -1,12 +1,14 @@
 """In-tree build of the HIP/C++ extensions.
 
-Four modules:
+Five modules:
   - ``pushcdn_gpu``  — CDNA4 data-plane kernels (csrc/hip/*.hip) + torch bindings,
                        compiled for gfx950 only.
   - ``pushcdn_gpu_ctl`` — device-state maintenance kernels
                        (csrc/hip/membership.hip) + torch bindings, gfx950 only.
   - ``pushcdn_gpu_acct`` — per-recipient loss-accounting kernels
                        (csrc/hip/accounting.hip) + torch bindings, gfx950 only.
+  - ``pushcdn_gpu_drain`` — the framed-drain kernels
+                       (csrc/hip/framed_drain.hip) + torch bindings, gfx950 only.
   - ``pushcdn_core`` — host C++ (wire serde, BLS-over-BN254, CRDT) via pybind11.
 
 Everything builds into ``<repo>/build/`` (in-tree, so the .so files travel to
@@ -44,6 +46,13 @@ GPU_ACCT_BUILD_DIR = BUILD_DIR / "acct"
 GPU_ACCT_SOURCES = [
     CSRC / "gpu_acct_bindings.cpp",
     CSRC / "hip" / "accounting.hip",
+]
+
+# And the framed drain's.
+GPU_DRAIN_BUILD_DIR = BUILD_DIR / "drain"
+GPU_DRAIN_SOURCES = [
+    CSRC / "gpu_drain_bindings.cpp",
+    CSRC / "hip" / "framed_drain.hip",
 ]
 
 os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
@@ -124,6 +133,17 @@ def build_gpu_acct(verbose: bool = False):
 def load_gpu_acct_prebuilt():
     """load_gpu_prebuilt for the loss-accounting extension."""
     return _load_prebuilt("pushcdn_gpu_acct", GPU_ACCT_BUILD_DIR / "pushcdn_gpu_acct.so")
+
+
+def build_gpu_drain(verbose: bool = False):
+    """Compile (if needed) and load the framed-drain extension
+    (K11 frame_rings). Returns the module."""
+    return _build_torch_ext("pushcdn_gpu_drain", GPU_DRAIN_SOURCES, GPU_DRAIN_BUILD_DIR, verbose)
+
+
+def load_gpu_drain_prebuilt():
+    """load_gpu_prebuilt for the framed-drain extension."""
+    return _load_prebuilt("pushcdn_gpu_drain", GPU_DRAIN_BUILD_DIR / "pushcdn_gpu_drain.so")
 
 
 CORE_SOURCES = [CSRC / "core_bindings.cpp"]

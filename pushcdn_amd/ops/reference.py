@@ -17,7 +17,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from ..utils.keyhash import as_i64 as _i64, fnv1a64
-from .ring_format import REF_FLAG, ring_rec
+from .ring_format import FRAME_SORT_MAX, REF_FLAG, ring_rec
 
 
 @dataclass
@@ -502,3 +502,67 @@ def build_direct_table(entries: List[Tuple[int, int]], size: int) -> Tuple[torch
             # DirectMap admits no more entries than slots: not reached from it
             raise RuntimeError(f"no free slot in a table of {size}")
     return keys, vals
+
+
+def frame_rings(
+    egress: torch.Tensor,      # uint8 [R * ring_bytes]
+    ring_bytes: int,
+    wpos: torch.Tensor,        # int64 [R], only read
+    dst_off: torch.Tensor,     # int64 [R], the exclusive scan of wpos
+    staging: torch.Tensor,     # uint8, mutated
+    frame_len: torch.Tensor,   # int64 [R], mutated
+    frame_cnt: torch.Tensor,   # int32 [R], mutated
+) -> None:
+    """Model of K11 (csrc/hip/framed_drain.hip): ring r's records as
+    [u32 big-endian len][body] frames at staging[dst_off[r]:], frame_len[r]
+    bytes of frame_cnt[r] frames, in seq order (circular-minimum base,
+    ascending (seq - base) mod 2^32, ties in ring order).
+
+    The cursor is clamped to [0, ring_bytes].  A record whose len has
+    REF_FLAG set, exceeds MAX_MESSAGE_SIZE or does not fit below the cursor
+    ends the ring there; the records before it are framed.  A ring is in
+    order when no record's seq is circularly below its predecessor's; one
+    that is not and holds more than FRAME_SORT_MAX records is copied raw
+    (frame_cnt -1, frame_len = the cursor).  A region that leaves the staging
+    buffer is treated as an empty ring."""
+    import numpy as np
+
+    from ..proto.message import MAX_MESSAGE_SIZE
+
+    u32 = 0xFFFFFFFF
+    eg = egress.numpy()
+    st = staging.numpy()
+    for r in range(wpos.shape[0]):
+        used = min(max(int(wpos[r]), 0), ring_bytes)
+        off = int(dst_off[r])
+        frame_len[r] = 0
+        frame_cnt[r] = 0
+        if used < 16 or off < 0 or off + used > st.shape[0]:
+            continue
+        ring = eg[r * ring_bytes : r * ring_bytes + used].tobytes()
+        recs = []   # (seq, body)
+        pos = 0
+        while pos + 16 <= used:
+            length = int.from_bytes(ring[pos : pos + 4], "little")
+            if length & REF_FLAG or length > MAX_MESSAGE_SIZE or pos + 16 + length > used:
+                break
+            recs.append((int.from_bytes(ring[pos + 4 : pos + 8], "little"),
+                         ring[pos + 16 : pos + 16 + length]))
+            pos += ring_rec(length)
+        in_order = all(((b[0] - a[0]) & u32) <= 0x80000000 for a, b in zip(recs, recs[1:]))
+        if not in_order:
+            if len(recs) > FRAME_SORT_MAX:
+                st[off : off + used] = eg[r * ring_bytes : r * ring_bytes + used]
+                frame_len[r] = used
+                frame_cnt[r] = -1
+                continue
+            base = recs[0][0]
+            for seq, _ in recs:
+                if (seq - base) & u32 > 0x80000000:
+                    base = seq
+            recs.sort(key=lambda rec: (rec[0] - base) & u32)   # stable: ties in ring order
+        framed = b"".join(len(body).to_bytes(4, "big") + body for _, body in recs)
+        assert len(framed) <= used
+        st[off : off + len(framed)] = np.frombuffer(framed, dtype=np.uint8)
+        frame_len[r] = len(framed)
+        frame_cnt[r] = len(recs)

@@ -12,6 +12,9 @@ from typing import List, Tuple
 
 RING_ALIGN = 16
 REF_FLAG = 0x80000000  # top bit of a record's len word: by-reference record
+# The framed drain sorts an out-of-order ring of at most this many records;
+# one with more comes back raw.  Host mirror of csrc/hip/framed_drain.h.
+FRAME_SORT_MAX = 4096
 
 
 def ring_rec(length: int) -> int:
@@ -63,4 +66,23 @@ def parse_ring_records(ring: bytes, wpos: int, refbuf=None) -> List[Tuple[int, b
             if (s_ - base) & 0xFFFFFFFF > 0x80000000:
                 base = s_
         out.sort(key=lambda r: (r[0] - base) & 0xFFFFFFFF)
+    return out
+
+
+def parse_frames(buf) -> List[bytes]:
+    """Split socket-ready frames, [u32 big-endian length][body] back to back
+    (what the framed drain leaves per recipient), into their bodies.  Strict:
+    the frames must tile `buf` exactly, else ValueError."""
+    buf = bytes(buf)
+    out = []
+    pos = 0
+    while pos < len(buf):
+        if pos + 4 > len(buf):
+            raise ValueError(f"{len(buf) - pos} stray bytes after the last frame")
+        length = int.from_bytes(buf[pos : pos + 4], "big")
+        if pos + 4 + length > len(buf):
+            raise ValueError(
+                f"frame at {pos} claims {length} bytes, {len(buf) - pos - 4} are left")
+        out.append(buf[pos + 4 : pos + 4 + length])
+        pos += 4 + length
     return out
